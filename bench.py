@@ -19,6 +19,10 @@ tokens the path has, the collective timed with HIP events against th
 Rank 0 prints ONE JSON line: the bench contract + `roofline` (dominant kernel = the bf16 MFMA GEMM, timed live with
 HIP events inside the timed region), `cpu_baseline` (the CPU oracle timed on this host, N=1 only), plus the log-mel
 kernel's HBM figure and an AF3-7B-shape greedy-decode leg (decode tokens/s, the second half of BASELINE's metric).
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the timed path returned in its last step as DIR/<name>.npy
+(float32; integer outputs as float64), at most 64 MB in all (see `dump_outputs`).  Inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,11 +38,20 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
+def _int_at_least(lo):
+    def conv(v):
+        n = int(v)
+        if n < lo:
+            raise argparse.ArgumentTypeError(f"must be >= {lo}, got {n}")
+        return n
+    return conv
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=_int_at_least(1), default=10, help="timed steps (ms_per_step = their wall time / steps)")
+    ap.add_argument("--warmup", type=_int_at_least(0), default=3)
     ap.add_argument("--batch", type=int, default=32, help="30-s clips per GPU per step")
     ap.add_argument("--no-decode", action="store_true", help="skip the AF3-7B decode leg")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
@@ -52,6 +65,8 @@ def parse_args(argv=None):
     ap.add_argument("--decode-steps", type=int, default=128)
     ap.add_argument("--decode-batch", type=int, default=8)
     ap.add_argument("--decode-fp8", action="store_true", help="--workload decode: W8A16 weights instead of bf16")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0; <= 64 MB in all, larger outputs as a seeded row sample)")
     ap.add_argument("--selftest-rendezvous", action="store_true",
                     help="launcher self-test (CPU, gloo): ranks rendezvous, barrier, reduce a fake elapsed time, gather one small tensor; no GPU work")
     return ap.parse_args(argv)
@@ -244,6 +259,38 @@ class BoardSampler:
             cap = None
         return {"shader_clock_mhz_median": mhz, "board_power_w_median": w, "board_power_cap_w": cap, "samples": len(sm),
                 "what": "hwmon freq1_input / power1_input of this GPU sampled every 10 ms over the timed steps (all kernels of the step, not the GEMM alone)"}
+
+
+DUMP_BYTES_MAX = 64_000_000       # --dump-outputs: cap on the data of all files written
+
+
+def _dump_sample(t, budget_bytes, seed):
+    """`t` as the host array --dump-outputs writes: float32 (float64 for integer dtypes), whole if it fits in `budget_bytes`, else
+    a fixed seeded choice of rows of its last dimension (torch.randperm on a CPU generator seeded with `seed`, the first rows that
+    fit, in ascending row order) as a [rows, t.shape[-1]] array.  The choice depends only on t's shape, the budget and the seed."""
+    import numpy as np
+    t = t.detach()
+    dt = torch.float32 if t.is_floating_point() else torch.float64
+    isz = 4 if dt is torch.float32 else 8
+    if t.numel() * isz <= budget_bytes:
+        return t.to(dt).cpu().numpy()
+    rows = t.reshape(-1, t.shape[-1])
+    n = budget_bytes // (rows.shape[1] * isz)
+    if n < 1:
+        raise ValueError(f"--dump-outputs: one row of {tuple(t.shape)} exceeds {budget_bytes} bytes")
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(rows.shape[0], generator=g)[:n].sort().values
+    return np.ascontiguousarray(rows[idx.to(rows.device)].to(dt).cpu().numpy())
+
+
+def dump_outputs(directory, outputs):
+    """Write each named tensor of `outputs` as `directory`/<name>.npy; the byte budget is split evenly between them and a tensor
+    that does not fit its share is written as a seeded row sample (`_dump_sample`)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_BYTES_MAX - 4096 * len(outputs)) // len(outputs)        # 4 KiB per file left for the .npy header
+    for i, (name, t) in enumerate(outputs.items()):
+        np.save(os.path.join(directory, name + ".npy"), _dump_sample(t, share, seed=1234 + i))
 
 
 def pmc_traffic():
@@ -508,7 +555,7 @@ def _rccl_version():
         return None
 
 
-def long_audio_workload(args, device, dist, rank, world, enc, fe, with_llm=True, steps=None, warmup=None):
+def long_audio_workload(args, device, dist, rank, world, enc, fe, with_llm=True, steps=None, warmup=None, dump_dir=None):
     """BASELINE configs[3]: 4 x 10-minute clips = 80 windows of 30 s, sharded over the ranks in contiguous blocks; each rank
     generates / uploads ONLY its own block, runs log-mel + encoder on it, and ONE all_gather_into_tensor returns every window's
     [750, 1280] bf16 tokens to every rank (timed on its own with HIP events, against the xGMI figure of SURVEY 8d); then, with
@@ -552,6 +599,8 @@ def long_audio_workload(args, device, dist, rank, world, enc, fe, with_llm=True,
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert tokens.shape[0] == W
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"long_audio_tokens": tokens})
     gather_ms = [tm["gather_ev"][0].elapsed_time(tm["gather_ev"][1]) for tm in gathers if "gather_ev" in tm]
     rehearsal = os.environ.get("AFHIP_BENCH_REHEARSAL") == "1"
     res = {"metric": "audio-seconds encoded/sec (long audio: log-mel + AF-Whisper encoder over window shards + token all-gather)",
@@ -644,6 +693,8 @@ def decode_only_workload(args, device, enc, fe):
     hyp, _, cache = model._greedy_device_loop(hyp[:, -1:, :], cache, "text", n_steps, poll=10 ** 9)
     torch.cuda.synchronize()
     dt_s = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"decode_tokens": hyp})
     wbytes = 1 if args.decode_fp8 else 2
     model._allowed_intervals("text")
     head_rows = model._allowed_hi.get("text") or n_vocab
@@ -694,7 +745,7 @@ def main():
         return
     if args.workload == "long_audio":
         enc = build_encoder(device, dtype, None)
-        res = long_audio_workload(args, device, dist, rank, world, enc, fe)
+        res = long_audio_workload(args, device, dist, rank, world, enc, fe, dump_dir=args.dump_outputs)
         if dist is not None:
             gathered = [None] * world
             dist.all_gather_object(gathered, res.get("llm_per_owned_clip"))
@@ -742,6 +793,8 @@ def main():
     elapsed = time.perf_counter() - t0
     board_info = board.stop()
     fence()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"encoder_out": out})        # [B, 1500, 1280] of the last timed step
     # the dominant kernel = gemm_pp_kernel (128 of the 130 GEMM launches of a forward, > 99 % of its FLOPs); the two
     # implicit-conv stem launches (gemm256_kernel) are collected separately
     n_l, ms, fl = C.c_int(), C.c_double(), C.c_double()

@@ -5,16 +5,17 @@ registers: reported, not an error).  Also fails on any FLAT memory instruction: 
 flat_load / flat_store means an address space got lost (an opaque `asm volatile("" : "+s"(ptr))` copy does that) -- round 4 found the decode
 GEMMs streaming their weights through flat loads (lgkmcnt waits of the LDS combine then drained the weight window) and the log-mel FFT reading
 its LDS tables through them.  usage: python tools/check_spills.py [file.hip ...]"""
-import glob, os, re, subprocess, sys
+import glob, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "audio-intelligence_amd", "csrc")
 extra = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "logmel.hip": ["-fno-slp-vectorize"],
          "attention_enc.hip": ["-Wno-inline-asm", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-fno-slp-vectorize"]}
 files = sys.argv[1:] or sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 bad = 0
+tmp = tempfile.TemporaryDirectory(prefix="check_spills_")      # private to this run: a fixed shared path collides with other users' runs
 for f in files:
     base = os.path.basename(f)
-    out = f"/tmp/spills_{base}.s"
+    out = os.path.join(tmp.name, base + ".s")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S", f, "-o", out] + extra.get(base, []),
                    check=True, stderr=subprocess.DEVNULL)
     txt = open(out).read()
