@@ -101,6 +101,9 @@ SIGNATURES = {
     "afhip_log_mel_tables_host": (_I, [_P, _P]),
     "afhip_log_mel_workspace_bytes": (_Z, [_I]),
     "afhip_log_mel": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "afhip_resample_plan": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "afhip_resample_tables_host": (_I, [_I, _I, _P]),
+    "afhip_resample": (_I, [_P, _I, _P, C.c_longlong, _P, C.c_longlong, _I, C.c_longlong, _I, _I, _P, _P]),
     "afhip_gemm": (_I, [C.POINTER(GemmArgs), _P]),
     "afhip_gemm_skinny": (_I, [C.POINTER(GemmArgs), _P]),
     "afhip_prof_enable": (_I, [_I]),

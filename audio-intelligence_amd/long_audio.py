@@ -15,6 +15,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .multimodal_io import resample
+
 WINDOW_SAMPLES = 480000
 
 
@@ -133,39 +135,67 @@ def build_long_prompt(prompt_ids: Sequence[int], n_samples: int, text_offset: in
     return seq, entries
 
 
+def _resampled_windows(clips, spans, sample_rate: int, dev) -> torch.Tensor:
+    """[len(spans), 480000] f32 on `dev`: window (c, a, b) holds outputs [a, b) of clip c resampled to 16 kHz, zeros after.  Only the
+    input span each window reads is uploaded (one host buffer, one copy); each window is one launch with its own m0."""
+    plan = [resample.input_span(a, b, len(clips[c]), sample_rate, 16000) for c, a, b in spans]
+    width = max([s1 - s0 for s0, s1, _ in plan] + [1])
+    host = torch.zeros((len(spans), width), dtype=torch.float32)
+    for i, ((c, _, _), (s0, s1, _)) in enumerate(zip(spans, plan)):
+        host[i, : s1 - s0] = torch.from_numpy(np.ascontiguousarray(clips[c][s0:s1], dtype=np.float32))
+    x = host.to(dev)
+    wins = torch.zeros((len(spans), WINDOW_SAMPLES), dtype=torch.float32, device=dev)
+    for i, ((_, a, b), (s0, s1, m0)) in enumerate(zip(spans, plan)):
+        y, _ = resample.resample_device(x[i: i + 1], sample_rate, 16000, lengths=[s1 - s0], m0=m0, n_out=b - a)
+        wins[i, : b - a] = y[0]
+    return wins
+
+
 @torch.no_grad()
 def long_audio_inference(model, audio_io, clips: Sequence[np.ndarray], prompts: Sequence[Sequence[int]], inference_config: dict,
                          enforce_modality: Optional[str] = "text", group: Optional[dist.ProcessGroup] = None,
-                         io_name: str = "continuous_audio", timing: Optional[dict] = None):
+                         io_name: str = "continuous_audio", timing: Optional[dict] = None, sample_rate: int = 16000):
     """Config 4 end to end on one node.  `clips`: 16 kHz mono waveforms of any length, the same list on every rank (host memory; each rank uploads only its own windows); `prompts`: text
     ids per clip.  Steps: (1) every clip is cut into 30-s windows and ALL windows of the batch are sharded over the ranks
     (window w of the flat list -> the rank whose contiguous block holds it); (2) log-mel + encoder on the local block;
     (3) one all-gather returns every window's [750, d] tokens to every rank; (4) clip c is owned by rank c % world: the owner
     builds the prompt with one (b, start, len) entry per window, `_embed` projects + splices them (lm/parallel.py:277-282),
     then causal prefill and greedy decode exactly as `inference_segment` does for a short clip.
+    `sample_rate`: the rate of every clip, 16 kHz or a supported rate above it (resample.check_front_end_rate).  Above 16 kHz the windows are cut in the 16 kHz output domain (a clip of n
+    samples has ceil(n 16000 / sample_rate) of them); each rank uploads, per window it owns, only the input span that window reads
+    (+-K taps, resample.input_span) and resamples just the window's outputs from it on the GPU -- bit-identical to the same range of
+    the fully resampled clip (afhip.h, afhip_resample).
     Returns {clip_index: (token ids LongTensor [n, S], modality)} for the clips THIS rank owns (every clip when not distributed)."""
     dev = model.device
     dist_on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if dist_on else 0
     world = dist.get_world_size(group) if dist_on else 1
-    spans, owner_of = [], []
-    for c, wav in enumerate(clips):
-        for a, b in split_windows(len(wav)):
+    resampled = int(sample_rate) != 16000
+    if resampled:
+        resample.check_front_end_rate(sample_rate)
+    n16 = [resample.out_length(len(wav), sample_rate, 16000) if resampled else len(wav) for wav in clips]
+    spans = []
+    for c in range(len(clips)):
+        for a, b in split_windows(n16[c]):
             spans.append((c, a, b))
     W = len(spans)
     lo, hi = shard_range(W, rank, world)                  # this rank cuts, pads and uploads ONLY its own block of windows
-    wins = torch.zeros((hi - lo, WINDOW_SAMPLES), dtype=torch.float32)
-    for i, (c, a, b) in enumerate(spans[lo:hi]):
-        wins[i, : b - a] = torch.from_numpy(np.ascontiguousarray(clips[c][a:b], dtype=np.float32))
     n_valid = torch.tensor([b - a for _, a, b in spans[lo:hi]], dtype=torch.long)
-    tokens = encode_windows_sharded(make_tower_encode_fn(audio_io), wins.to(dev), n_valid.to(dev), group=group, timing=timing,
+    if resampled:
+        wins = _resampled_windows(clips, spans[lo:hi], int(sample_rate), dev)
+    else:
+        wins = torch.zeros((hi - lo, WINDOW_SAMPLES), dtype=torch.float32)
+        for i, (c, a, b) in enumerate(spans[lo:hi]):
+            wins[i, : b - a] = torch.from_numpy(np.ascontiguousarray(clips[c][a:b], dtype=np.float32))
+        wins = wins.to(dev)
+    tokens = encode_windows_sharded(make_tower_encode_fn(audio_io), wins, n_valid.to(dev), group=group, timing=timing,
                                     total_windows=W)
     text_offset = model.vocab_intervals["text"][0][0]
     results = {}
     for c, wav in enumerate(clips):
         if c % world != rank:
             continue
-        seq, entries = build_long_prompt(prompts[c], len(wav), text_offset, model.num_stream)
+        seq, entries = build_long_prompt(prompts[c], n16[c], text_offset, model.num_stream)
         idx = [i for i, (cc, _, _) in enumerate(spans) if cc == c]
         batch = {"seqs": seq[None].to(dev),
                  f"{io_name}_indices": torch.tensor([[0, s, n] for s, n in entries], dtype=torch.long),

@@ -12,6 +12,8 @@ import numpy as np
 import os
 import torch
 
+from .. import _lib as L
+from . import resample
 from .abs_io import AbsIO
 from .feature_extraction import WhisperFeatureExtractorHIP
 from .modeling_whisper import AFWhisperEncoder
@@ -68,7 +70,7 @@ class ContinuousAudioIO(AbsIO):
             raise RuntimeError("ContinuousAudioIO.preprocess runs the log-mel kernel on the GPU: call it in the main process "
                                "(DataLoader num_workers=0), or feed raw waveforms to encode_wav_batch")
         if fs != self.sample_rate:
-            raise ValueError(f"sampling rate {fs} != {self.sample_rate}: resample first (the reference calls librosa.resample, audio.py:1034)")
+            return self._preprocess_resampled(wav, int(fs))
         if len(wav.shape) > 1:
             wav = wav[0]
         if wav.shape[0] > self.n_samples:
@@ -79,6 +81,29 @@ class ContinuousAudioIO(AbsIO):
         original_samples = wav.shape[0]
         feat = self.processor(wav, sampling_rate=self.sample_rate, return_tensors="np")["input_features"][0].T
         after_length = self._after_length(original_samples)
+        paddings = np.zeros((after_length, 1)).astype(np.int32)
+        return paddings, (after_length, np.ascontiguousarray(feat)), paddings
+
+    def _preprocess_resampled(self, wav, fs: int):
+        """preprocess for a clip at fs > 16 kHz, in the reference's order (audio.py:1031-1044): resample (GPU), first channel, truncate
+        to n_samples, then the log-mel of the device buffer.  Only the first channel is uploaded and resampled -- the reference resamples
+        every channel and keeps wav[0], the same samples.  Only the first n_samples outputs are computed: each output depends on the
+        input alone, so they equal the head of the fully resampled clip."""
+        resample.check_front_end_rate(fs, self.sample_rate)     # below 16 kHz, or an unsupported pair: raises here
+        wav = np.asarray(wav)
+        if wav.ndim > 1:
+            wav = wav[0]
+        n_res = resample.out_length(wav.shape[0], fs, self.sample_rate)
+        if n_res > self.n_samples:
+            print(f"Warning: Input audio is too long to process, will truncate to {self.n_samples} samples")
+        n = min(n_res, self.n_samples)
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+        if dev is None:
+            L.lib()  # raises: no CPU fallback
+        x = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)).to(dev)
+        y, _ = resample.resample_device(x[None], fs, self.sample_rate, n_out=n)
+        feat = self.processor.extract_device(y, layout="bct")[0].cpu().numpy().T
+        after_length = self._after_length(n)
         paddings = np.zeros((after_length, 1)).astype(np.int32)
         return paddings, (after_length, np.ascontiguousarray(feat)), paddings
 
@@ -108,9 +133,18 @@ class ContinuousAudioIO(AbsIO):
         return [out[i, : int(out_len[i])] for i in range(out.shape[0])]
 
     @torch.no_grad()
-    def encode_wav_batch(self, wav: torch.Tensor, length: torch.Tensor = None) -> List[torch.Tensor]:
-        """Fused device path: raw 16 kHz clips [B, n<=480000] f32 on the GPU -> encoder outputs, no host hop.
-        `length` as in encode_batch (default: pipeline convention, 3000)."""
+    def encode_wav_batch(self, wav: torch.Tensor, length: torch.Tensor = None, sample_rate: int = 16000,
+                         n_valid: torch.Tensor = None) -> List[torch.Tensor]:
+        """Fused device path: raw clips [B, n] f32 on the GPU -> encoder outputs, no host hop.
+        `length` as in encode_batch (default: pipeline convention, 3000).  16 kHz clips go straight to the log-mel (n <= 480000 is used,
+        as before).  Clips at a supported `sample_rate` above 16 kHz are resampled on the GPU first (the first 480000 outputs, the reference's
+        truncation), then the log-mel reads the resampled buffer; `n_valid` [B] is then each clip's valid samples at `sample_rate`
+        (default: n), and outputs past a clip's own resampled length are zeros, as padding of a 16 kHz batch is."""
+        if sample_rate != self.sample_rate:
+            resample.check_front_end_rate(sample_rate, self.sample_rate)
+            n_in = wav.shape[1] if n_valid is None else None
+            n = self.n_samples if n_in is None else min(resample.out_length(n_in, sample_rate, self.sample_rate), self.n_samples)
+            wav, _ = resample.resample_device(wav, sample_rate, self.sample_rate, lengths=n_valid, n_out=n)
         mel = self.processor.extract_device(wav, layout="btc", dtype=self.dtype)
         if length is None:
             length = torch.full((wav.shape[0],), 3000, dtype=torch.long)

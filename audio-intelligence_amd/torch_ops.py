@@ -216,3 +216,21 @@ for _name, (_cuda, _meta) in _impls.items():
     _lib_impl.impl(_name, _cuda, "CUDA")          # "CUDA" is the HIP device key on ROCm builds; there is no CPU kernel (no fallback)
     _lib_impl.impl(_name, _meta, "Meta")
 OP_NAMES = sorted(_impls)
+
+# the audio front end's resampler (afhip_resample, multimodal_io/resample.py): (wav [B, n] f32, n_in [B] int32) -> outputs
+# [m0, m0 + n_out) of every clip at target_sr.  Registered on its own, next to the op set above.
+_lib_def.define("resample(Tensor wav, Tensor n_in, int orig_sr, int target_sr, int m0, int n_out) -> Tensor")
+
+
+def _resample(wav, n_in, orig_sr, target_sr, m0, n_out):
+    from .multimodal_io.resample import resample_device
+    y, _ = resample_device(wav, orig_sr, target_sr, lengths=n_in, m0=m0, n_out=n_out)
+    return y.clone() if orig_sr == target_sr else y       # an op's output never aliases its input
+
+
+def _resample_meta(wav, n_in, orig_sr, target_sr, m0, n_out):
+    return wav.new_empty((wav.shape[0], n_out), dtype=torch.float32)
+
+
+_lib_impl.impl("resample", _resample, "CUDA")
+_lib_impl.impl("resample", _resample_meta, "Meta")

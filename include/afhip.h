@@ -64,6 +64,32 @@ int afhip_log_mel(const float* wav, int B, int n_samples, int wav_stride, void* 
                   const float* tables, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * resampler in front of the log-mel.  Replaces librosa.resample(wav, orig_sr=fs, target_sr=16000) in
+ * multimodal_io/audio.py:1031-1034 (ContinuousAudioIO.preprocess) for audio at any other rate.  Band-limited,
+ * rational ratio, fp32: g = gcd(fs_in, fs_out), L = fs_out/g, M = fs_in/g, f_min = min(fs_in, fs_out);
+ * Kaiser-windowed sinc, cutoff fc = 0.955 f_min/2, transition D = 0.09 f_min/2, A = 110 dB, beta = 0.1102 (A - 8.7),
+ * half-width T_h = (A - 7.95) / (4.57 2 pi D) s, h(tau) = (2 fc/fs_in) sinc(2 fc tau) I0(beta sqrt(1 - (tau/T_h)^2)) / I0(beta)
+ * for |tau| <= T_h, 0 outside; no per-phase renormalisation.  Same class of filter as soxr's HQ recipe (linear phase,
+ * ~20 bit, alias-free above the output Nyquist), not soxr's filter.
+ * Sample convention (librosa's, with its fix_length): output m sits at m/fs_out, input n at n/fs_in, input outside
+ * [0, n_in) is zero, n_out = ceil(n_in fs_out / fs_in).  Polyphase: q = floor(m M / L), p = (m M) mod L,
+ * K = ceil(T_h fs_in), y[m] = sum_{k=-K..K} x[q+k] H[p][k+K], H[p][k+K] = h((p/L - k)/fs_in).
+ *   plan       L, M, K, T_pad (= 2K+1 rounded up to a multiple of 4) of a rate pair; -1 + message for a pair outside
+ *              [1, 384000] Hz, with L > 1024, or needing more than 16381 taps per output
+ *   tables     afhip_resample_tables_host fills a HOST buffer of L * T_pad f32: [L][T_pad], built in double, rounded once,
+ *              zero padded; the caller uploads it once per rate pair
+ *   resample   x [B, *] f32 rows of x_stride floats with n_in[b] (device int32) valid samples each (held to [0, x_stride]);
+ *              writes outputs [m0, m0 + n_out_max) of every clip to y [B, y_stride]: position m - m0; outputs at or past the
+ *              clip's own n_out are exact zeros.  x_stride <= 2^28.  The sum order of output m depends only on m mod L',
+ *              L' = L * 16 / gcd(L, 16): shifting the input by j M samples and m0 by j L with j a multiple of 16 / gcd(L, 16)
+ *              gives bit-identical outputs (windows of a long clip resampled from their own input span).
+ */
+int afhip_resample_plan(int fs_in, int fs_out, int* L, int* M, int* K, int* T_pad);
+int afhip_resample_tables_host(int fs_in, int fs_out, void* host_buf);
+int afhip_resample(const float* x, int B, const int32_t* n_in, long long x_stride, float* y, long long m0, int n_out_max,
+                   long long y_stride, int fs_in, int fs_out, const float* tables, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GEMM  C[M,N] = epilogue(A[M,K] . W[N,K]^T): the arithmetic of every nn.Linear / nn.Conv1d on the path
  * (modeling_whisper.py:132-135,467-468,614-615; lm/parallel.py:146-149; modeling_qwen2.py:35-49,195-235).
  *   epilogue: + bias[N]  -> act -> + residual[m % res_row_mod or m, N]
