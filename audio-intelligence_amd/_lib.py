@@ -91,6 +91,14 @@ class SampleArgs(C.Structure):
                 ("one_minus_cfg", C.c_float)]
 
 
+class SampleFilterArgs(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("cfg_logits", C.c_void_p), ("cfg", C.c_float), ("one_minus_cfg", C.c_float),
+                ("model_dtype", C.c_int), ("rows", C.c_int), ("V", C.c_int), ("ld", C.c_int),
+                ("allowed", C.c_void_p), ("n_iv", C.c_int), ("penalty_ids", C.c_void_p), ("n_ids", C.c_void_p), ("max_ids", C.c_int),
+                ("penalty", C.c_float), ("temperature", C.c_float), ("top_k", C.c_int), ("exact_k", C.c_int), ("top_p", C.c_float),
+                ("u", C.c_void_p), ("scores", C.c_void_p), ("ld_scores", C.c_int), ("token", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/afhip.h one to one (tests/test_cabi.py checks the header against this)
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -130,6 +138,8 @@ SIGNATURES = {
     "afhip_masked_argmax_workspace_bytes": (_Z, [_I]),
     "afhip_masked_argmax": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _Z, _P]),
     "afhip_sample_topk": (_I, [C.POINTER(SampleArgs), _P]),
+    "afhip_sample_filter_workspace_bytes": (_Z, [_I, _I]),
+    "afhip_sample_filter": (_I, [C.POINTER(SampleFilterArgs), _P, _Z, _P]),
     "afhip_llm_decode_step": (_I, [C.POINTER(LlmWeights), C.POINTER(KvCache), C.POINTER(DecodeState), _I, _I, _I, _P, _Z, _P]),
 }
 

@@ -2,7 +2,7 @@
 // inverse-CDF draw, one workgroup per (sequence, stream) row.  Mirrors lm/parallel.py:489-492 (logits * cfg + cfg_logits * (1 - cfg),
 // masked_fill_ with the modality mask) and :603-608 (topk -> softmax(values / temperature) -> multinomial -> gather).
 // The multinomial draw is taken from a caller-supplied uniform per row (same distribution, no RNG stream to reproduce).
-#include "common.h"
+#include "sample_mix.h"
 
 namespace {
 
@@ -24,22 +24,10 @@ struct SampleP {
     int64_t* token;
 };
 
-// the value the reference's tensors hold at (row, id): model-dtype logits, mixed with three separately rounded tensor ops
+// the value the reference's tensors hold at (row, id) (sample_mix.h)
 template <bool RB>
 __device__ __forceinline__ float mixed_value(const SampleP& p, const float* row, const float* crow, int i) {
-#pragma clang fp contract(off)
-    float v = row[i];
-    if (RB) v = (float)(bf16)v;
-    if (crow) {
-        float c = crow[i];
-        if (RB) c = (float)(bf16)c;
-        float a = v * p.cfg;
-        float b = c * p.one_minus_cfg;
-        if (RB) { a = (float)(bf16)a; b = (float)(bf16)b; }
-        v = a + b;
-        if (RB) v = (float)(bf16)v;
-    }
-    return v;
+    return cfg_mixed_value<RB>(row, crow, i, p.cfg, p.one_minus_cfg);
 }
 
 // (v, i) precedes (w, j) in the output order: larger value first, ties by smaller id

@@ -493,13 +493,22 @@ class ParallelLLM(nn.Module):
     @torch.no_grad()
     def _topk_probs(self, logits_f32: torch.Tensor, allowed: torch.Tensor, topk: int, temperature: float,
                     cfg_logits: Optional[torch.Tensor] = None, cfg: float = 1.0, model_dtype=None, u: Optional[torch.Tensor] = None):
-        """afhip_sample_topk over rows [n, V] (f32): (topk ids [n,k] int32, mixed logits [n,k], probabilities [n,k], drawn ids [n] | None).
+        """afhip_sample_topk over rows [n, V] (f32): (topk ids [n,k] int32, mixed logits [n,k], probabilities [n,k], drawn ids [n] | None);
+        k > 64: afhip_sample_filter in exact top-k mode, (None, None, None, drawn ids [n]) -- u is then required.
         `allowed` [n, n_iv, 2] int32 id intervals per row; cfg_logits / cfg: the guidance mix of lm/parallel.py:489-492."""
         lib = L.lib()
         n, V = logits_f32.shape
         dev = logits_f32.device
-        if not 1 <= int(topk) <= 64:
-            raise ValueError(f"topk={topk}: afhip_sample_topk selects at most 64 candidates per row (the reference accepts any k; conf/inference.yaml uses 20)")
+        if not 1 <= int(topk) <= max(64, V):
+            raise ValueError(f"topk={topk}: must be in [1, V={V}]")
+        if topk > 64:
+            # afhip_sample_topk keeps its list in registers (k <= 64); larger k goes to the full-vocabulary filter-and-draw in exact
+            # mode (k ids, ties by smaller id), which returns the drawn id only
+            if u is None:
+                raise NotImplementedError(f"topk={topk} > 64: only the drawn ids are available (no top-k list for an injected sampler)")
+            tok = ops.sample_filter(logits_f32, temperature=temperature, top_k=int(topk), exact_k=True, allowed=allowed,
+                                    cfg_logits=cfg_logits, cfg=cfg, model_dtype=model_dtype if model_dtype is not None else self.dtype, u=u)
+            return None, None, None, tok
         idx = torch.empty((n, topk), dtype=torch.int32, device=dev)
         val = torch.empty((n, topk), dtype=torch.float32, device=dev)
         prob = torch.empty((n, topk), dtype=torch.float32, device=dev)
@@ -521,6 +530,11 @@ class ParallelLLM(nn.Module):
         (tests), receives (topk ids [B,T,S,k], probabilities) and returns the inner indices instead."""
         if temperature == 0:
             return logits.argmax(-1)
+        if not 1 <= int(topk) <= 64:
+            # this form hands the top-k LIST to an injected sampler, which only afhip_sample_topk produces; the decode loop
+            # (inference_segment -> _topk_probs) draws for any k <= V through afhip_sample_filter
+            raise ValueError(f"topk={topk}: _logits_to_token uses afhip_sample_topk, which selects at most 64 candidates per row "
+                             "(inference_segment serves any k up to the vocabulary size)")
         shp = logits.shape[:-1]
         rows = logits.reshape(-1, logits.shape[-1]).float().contiguous()
         whole = torch.tensor([[[0, rows.shape[1]]]], dtype=torch.int32, device=rows.device).expand(rows.shape[0], 1, 2).contiguous()

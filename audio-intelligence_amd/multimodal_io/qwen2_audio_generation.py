@@ -29,6 +29,54 @@ def _get(cfg, name, default=None):
     return cfg.get(name, default) if isinstance(cfg, dict) else getattr(cfg, name, default)
 
 
+# GenerationConfig fields this generate() serves; every other processor / search knob raises NotImplementedError when set to a
+# non-neutral value (the neutral values are those under which GenerationMixin._get_logits_processor adds nothing)
+_SERVED = ("max_new_tokens", "max_length", "eos_token_id", "pad_token_id", "do_sample", "temperature", "top_k", "top_p",
+           "repetition_penalty", "return_dict_in_generate", "output_scores", "output_logits")
+_SET = lambda v: v is not None
+_UNSERVED = {
+    "min_p": _SET, "top_h": _SET, "typical_p": lambda v: v is not None and v < 1.0,
+    "epsilon_cutoff": lambda v: v is not None and 0.0 < v < 1.0, "eta_cutoff": lambda v: v is not None and 0.0 < v < 1.0,
+    "num_beams": lambda v: v is not None and v > 1, "num_beam_groups": lambda v: v is not None and v > 1,
+    "num_return_sequences": lambda v: v is not None and v > 1, "diversity_penalty": lambda v: v is not None and v != 0.0,
+    "penalty_alpha": lambda v: v is not None and v > 0, "no_repeat_ngram_size": lambda v: v is not None and v > 0,
+    "encoder_no_repeat_ngram_size": lambda v: v is not None and v > 0,
+    "encoder_repetition_penalty": lambda v: v is not None and v != 1.0, "bad_words_ids": _SET, "force_words_ids": _SET,
+    "constraints": _SET, "min_length": lambda v: v is not None and v > 0, "min_new_tokens": lambda v: v is not None and v > 0,
+    "sequence_bias": _SET, "suppress_tokens": _SET, "begin_suppress_tokens": _SET, "forced_bos_token_id": _SET,
+    "forced_eos_token_id": _SET, "exponential_decay_length_penalty": _SET, "guidance_scale": lambda v: v is not None and v != 1,
+    "renormalize_logits": lambda v: v is True, "remove_invalid_values": lambda v: v is True, "watermarking_config": _SET,
+    "stop_strings": _SET, "max_time": _SET, "output_attentions": lambda v: v is True, "output_hidden_states": lambda v: v is True,
+    "logits_processor": lambda v: v is not None and len(v) > 0, "stopping_criteria": lambda v: v is not None and len(v) > 0,
+    "prefix_allowed_tokens_fn": _SET, "assistant_model": _SET, "streamer": _SET, "prompt_lookup_num_tokens": _SET,
+    "dola_layers": _SET, "token_healing": lambda v: v is True,
+}
+_IGNORED = ("use_cache", "bos_token_id", "decoder_start_token_id", "early_stopping", "length_penalty", "cache_implementation",
+            "transformers_version", "synced_gpus")
+
+
+def _generation_knobs(generation_config, kwargs, **explicit) -> dict:
+    """GenerationConfig / dict + explicit arguments (which win) -> the served knobs; unserved knobs that are set raise."""
+    if generation_config is None:
+        base = {}
+    elif isinstance(generation_config, dict):
+        base = dict(generation_config)
+    elif hasattr(generation_config, "to_dict"):
+        base = generation_config.to_dict()
+    else:
+        base = dict(vars(generation_config))
+    for name, v in kwargs.items():
+        if name not in _UNSERVED and name not in _IGNORED:
+            raise TypeError(f"generate() got an unexpected keyword argument '{name}'")
+    merged = {**base, **kwargs}
+    for name, is_set in _UNSERVED.items():
+        if name in merged and is_set(merged[name]):
+            raise NotImplementedError(f"generate(): `{name}`={merged[name]!r} is not supported (served: {', '.join(_SERVED)})")
+    out = {n: base.get(n) for n in _SERVED}
+    out.update({n: v for n, v in explicit.items() if v is not None})
+    return out
+
+
 class _CausalLM(nn.Module):
     """`Qwen2ForCausalLM` parameter layout: `model.embed_tokens / layers / norm` + `lm_head` (no bias)."""
 
@@ -271,16 +319,115 @@ class Qwen2AudioForConditionalGeneration(nn.Module):
                              "feature_attention_mask": kwargs.get("feature_attention_mask", None)})
         return model_inputs
 
-    # ---- greedy generation (GenerationMixin.generate, do_sample=False)
+    # ---- generation (GenerationMixin.generate: greedy and multinomial sampling)
     @torch.no_grad()
-    def generate(self, input_ids, input_features=None, attention_mask=None, feature_attention_mask=None, max_new_tokens: int = 20,
-                 eos_token_id=None, pad_token_id=None):
-        """Greedy decoding: returns [B, L + n_new] = the prompt ids followed by the generated ones; a sequence that has emitted
-        `eos_token_id` is continued with `pad_token_id` (HF semantics), generation stops when every sequence has finished."""
-        dev = self.device
+    def generate(self, input_ids, input_features=None, attention_mask=None, feature_attention_mask=None, max_new_tokens: Optional[int] = None,
+                 eos_token_id=None, pad_token_id=None, do_sample: Optional[bool] = None, temperature: Optional[float] = None,
+                 top_k: Optional[int] = None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                 generation_config=None, return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None,
+                 output_logits: Optional[bool] = None, generator: Optional[torch.Generator] = None, **kwargs):
+        """Returns [B, L + n_new] = the prompt ids followed by the generated ones; a sequence that has emitted `eos_token_id` is continued
+        with `pad_token_id` (HF semantics), generation stops when every sequence has finished.
+
+        HF knobs, with GenerationMixin's semantics: `do_sample`, `temperature`, `top_k`, `top_p`, `repetition_penalty`, `max_length`,
+        taken from `generation_config` (a GenerationConfig or a dict) unless passed explicitly.  An unset or neutral knob applies no
+        processor (top_k None / 0, top_p >= 1, temperature None / 1, repetition_penalty None / 1); any other processor knob that is
+        set raises NotImplementedError.  The processors and the draw run in one HIP kernel (afhip_sample_filter); the draw takes one
+        `torch.rand(B, generator=generator)` per step (`generator` is an extension: a fixed seed gives a fixed token stream).
+        `return_dict_in_generate=True` returns a namespace with `sequences`, and `scores` (processed rows, `output_scores`) / `logits`
+        (raw rows, `output_logits`) as tuples of [B, V] f32 per step."""
+        cfg = _generation_knobs(generation_config, kwargs, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                                do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                return_dict_in_generate=return_dict_in_generate, output_scores=output_scores, output_logits=output_logits)
+        max_new = cfg.get("max_new_tokens")
+        if max_new is None:
+            max_new = cfg["max_length"] - input_ids.shape[1] if cfg.get("max_length") is not None else 20
+        rp = cfg.get("repetition_penalty")
+        sampling = bool(cfg.get("do_sample"))
+        want_dict = bool(cfg.get("return_dict_in_generate"))
+        if not sampling and rp in (None, 1.0) and not want_dict:
+            return self._generate_greedy(input_ids, input_features, attention_mask, feature_attention_mask, max_new,
+                                         cfg.get("eos_token_id"), cfg.get("pad_token_id"))
+        return self._generate_filtered(input_ids, input_features, attention_mask, feature_attention_mask, max_new, cfg, generator)
+
+    def _eos_pad(self, eos_token_id, pad_token_id):
         eos = eos_token_id if eos_token_id is not None else _get(self.config, "eos_token_id")
         eos = [] if eos is None else ([eos] if isinstance(eos, int) else list(eos))
         pad = pad_token_id if pad_token_id is not None else (self.pad_token_id if self.pad_token_id >= 0 else (eos[0] if eos else 0))
+        return eos, pad
+
+    @torch.no_grad()
+    def _generate_filtered(self, input_ids, input_features, attention_mask, feature_attention_mask, max_new_tokens, cfg, generator):
+        """Greedy with a repetition penalty, or multinomial sampling: every step's logits go through afhip_sample_filter."""
+        dev = self.device
+        eos, pad = self._eos_pad(cfg.get("eos_token_id"), cfg.get("pad_token_id"))
+        sampling = bool(cfg.get("do_sample"))
+        V = self.vocab_size
+        T = cfg.get("temperature") if sampling else None
+        T = 1.0 if T is None else float(T)
+        if not T > 0:
+            raise ValueError(f"`temperature` (={T}) has to be a strictly positive float")
+        k = cfg.get("top_k") if sampling else None
+        k = 0 if k is None else int(k)
+        if k < 0:
+            raise ValueError(f"`top_k` has to be a strictly positive integer, but is {k}")
+        p = cfg.get("top_p") if sampling else None
+        p = 1.0 if p is None or p >= 1.0 else float(p)
+        if p < 0:
+            raise ValueError(f"`top_p` has to be a float >= 0 and <= 1, but is {p}")
+        p = max(p, 2.0 ** -40)                                   # top_p = 0 keeps the top value (min_tokens_to_keep = 1)
+        rp = cfg.get("repetition_penalty")
+        rp = 1.0 if rp is None else float(rp)
+        if not rp > 0:
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+        out_scores, out_logits = bool(cfg.get("output_scores")), bool(cfg.get("output_logits"))
+        input_ids = input_ids.to(dev)
+        hid, cache, mask, _, _, _ = self._prefill(input_ids, input_features, attention_mask, feature_attention_mask, None, None, max_new_tokens)
+        B, W = input_ids.shape
+        nxt_logits = self._head(hid[torch.arange(B, device=dev), cache.seq_len.long() - 1]).to(self.dtype)
+        pen_ids = n_ids = None
+        if rp != 1.0:
+            # what RepetitionPenaltyLogitsProcessor sees: the caller's ids (pads and <|AUDIO|> placeholders included), then the
+            # generated ones -- a device buffer appended to in place, never rebuilt on the host
+            pen_ids = torch.empty((B, W + max_new_tokens), dtype=torch.int32, device=dev)
+            pen_ids[:, :W] = input_ids
+            n_ids = torch.full((B,), W, dtype=torch.int32, device=dev)
+        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        new, scores, raw = [], [], []
+        for step in range(max_new_tokens):
+            lg = nxt_logits.float().contiguous()
+            if out_logits:
+                raw.append(lg)
+            sc = torch.empty((B, V), dtype=torch.float32, device=dev) if out_scores else None
+            u = torch.rand(B, generator=generator, device=dev) if sampling else None
+            tok = ops.sample_filter(lg, temperature=T, top_k=min(k, V), top_p=p, penalty=rp, penalty_ids=pen_ids, n_ids=n_ids, u=u, scores=sc)
+            if out_scores:
+                scores.append(sc)
+            tok = torch.where(unfinished, tok, torch.full_like(tok, pad))
+            new.append(tok)
+            if pen_ids is not None:
+                pen_ids[:, W + step] = tok.to(torch.int32)
+                n_ids += 1
+            for e in eos:
+                unfinished = unfinished & (tok != e)
+            if not bool(unfinished.any()) or step == max_new_tokens - 1:
+                break
+            o = self.forward(input_ids=tok[:, None], past_key_values=cache, use_cache=True)
+            nxt_logits, cache = o.logits[:, -1], o.past_key_values
+        seqs = torch.cat([input_ids, torch.stack(new, dim=1)], dim=1)
+        if not cfg.get("return_dict_in_generate"):
+            return seqs
+        return SimpleNamespace(sequences=seqs, scores=tuple(scores) if out_scores else None, logits=tuple(raw) if out_logits else None,
+                               attentions=None, hidden_states=None, past_key_values=None)
+
+    # ---- greedy generation (GenerationMixin.generate, do_sample=False)
+    @torch.no_grad()
+    def _generate_greedy(self, input_ids, input_features=None, attention_mask=None, feature_attention_mask=None, max_new_tokens: int = 20,
+                         eos_token_id=None, pad_token_id=None):
+        """Greedy decoding: returns [B, L + n_new] = the prompt ids followed by the generated ones; a sequence that has emitted
+        `eos_token_id` is continued with `pad_token_id` (HF semantics), generation stops when every sequence has finished."""
+        dev = self.device
+        eos, pad = self._eos_pad(eos_token_id, pad_token_id)
         input_ids = input_ids.to(dev)
         hid, cache, mask, _, _, _ = self._prefill(input_ids, input_features, attention_mask, feature_attention_mask, None, None, max_new_tokens)
         B = input_ids.shape[0]

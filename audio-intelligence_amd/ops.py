@@ -314,3 +314,52 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         a.rope_cos, a.rope_sin = cos.data_ptr(), sin.data_ptr()
     L.check(lib.afhip_attention(C.byref(a), L.stream_ptr()))
     return out
+
+
+def sample_filter(logits: torch.Tensor, *, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, exact_k: bool = False,
+                  penalty: float = 1.0, penalty_ids: Optional[torch.Tensor] = None, n_ids: Optional[torch.Tensor] = None,
+                  allowed: Optional[torch.Tensor] = None, cfg_logits: Optional[torch.Tensor] = None, cfg: float = 1.0,
+                  model_dtype=torch.float32, u: Optional[torch.Tensor] = None, want_token: bool = True,
+                  scores: Optional[torch.Tensor] = None):
+    """afhip_sample_filter over f32 rows [n, V] (any row stride): penalty -> temperature -> top-k -> top-p -> draw at u [n]
+    (u None: first argmax).  penalty_ids [n, m] int32 with n_ids [n] int32 valid entries per row; allowed [n, n_iv, 2] int32;
+    cfg_logits: guidance mix `logits * cfg + cfg_logits * (1 - cfg)`.  scores [n, >= V] f32, when given, receives the processed rows
+    (-inf where removed).  Returns the drawn ids [n] int64 (or None)."""
+    lib = L.lib()
+    _chk(logits, "sample_filter.logits")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise L.AfhipError("sample_filter: logits must be f32 [n, V] with unit column stride")
+    n, V = logits.shape
+    dev = logits.device
+    for name, t, shape, dt in (("u", u, (n,), torch.float32), ("n_ids", n_ids, (n,), torch.int32), ("allowed", allowed, None, None),
+                               ("penalty_ids", penalty_ids, None, torch.int32), ("scores", scores, None, torch.float32)):
+        if t is None:
+            continue
+        _chk(t, f"sample_filter.{name}")
+        if t.shape[0] != n or (shape is not None and tuple(t.shape) != shape) or (dt is not None and t.dtype != dt) or t.stride(-1) != 1:
+            raise L.AfhipError(f"sample_filter: {name} must be {dt or 'int32'} with {n} rows (got {tuple(t.shape)} {t.dtype})")
+    if (penalty_ids is None) != (n_ids is None) or (scores is not None and scores.shape[1] < V):
+        raise L.AfhipError("sample_filter: penalty_ids and n_ids go together; scores needs >= V columns")
+    need = lib.afhip_sample_filter_workspace_bytes(n, V)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    tok = torch.empty(n, dtype=torch.int64, device=dev) if want_token else None
+    a = L.SampleFilterArgs()
+    a.logits, a.rows, a.V, a.ld = logits.data_ptr(), n, V, logits.stride(0)
+    if cfg_logits is not None:
+        if cfg_logits.stride() != logits.stride() or cfg_logits.dtype != torch.float32:
+            raise L.AfhipError("sample_filter: cfg_logits must be f32 with the strides of logits")
+        a.cfg_logits = cfg_logits.data_ptr()
+    a.cfg, a.one_minus_cfg = float(cfg), float(1.0 - cfg)          # (1 - cfg) in double, rounded once (afhip_sample_args)
+    a.model_dtype = L.dtype_code(model_dtype)
+    if allowed is not None:
+        allowed = allowed.to(device=dev, dtype=torch.int32).contiguous()
+        a.allowed, a.n_iv = allowed.data_ptr(), allowed.shape[1]
+    if penalty_ids is not None:
+        a.penalty_ids, a.n_ids, a.max_ids = penalty_ids.data_ptr(), n_ids.data_ptr(), penalty_ids.stride(0)
+    a.penalty, a.temperature, a.top_k, a.exact_k, a.top_p = float(penalty), float(temperature), int(top_k), int(bool(exact_k)), float(top_p)
+    a.u = u.data_ptr() if u is not None else None
+    if scores is not None:
+        a.scores, a.ld_scores = scores.data_ptr(), scores.stride(0)
+    a.token = tok.data_ptr() if tok is not None else None
+    L.check(lib.afhip_sample_filter(C.byref(a), C.c_void_p(ws.data_ptr()), need, L.stream_ptr()))
+    return tok

@@ -437,6 +437,42 @@ typedef struct {
 } afhip_sample_args;
 int afhip_sample_topk(const afhip_sample_args* args, void* stream);
 
+/* Full-vocabulary filter-and-draw (sample_filter.hip): per row of f32 logits, in the order transformers' GenerationMixin applies its
+ * processors -- [guidance mix + allowed-id intervals] -> repetition penalty -> temperature -> top-k -> top-p -> draw.
+ *   penalty      x < 0 ? x * pen : x / pen, once per DISTINCT id of the row's list (RepetitionPenaltyLogitsProcessor)
+ *   temperature  x / T (TemperatureLogitsWarper)
+ *   top-k        exact_k = 0: keep every id >= the k-th largest value, ties at the threshold all kept (TopKLogitsWarper);
+ *                exact_k = 1: keep exactly k ids, ties broken by smaller id (afhip_sample_topk's order)
+ *   top-p        TopPLogitsWarper: keep the largest values whose softmax mass (over the top-k survivors) strictly above them is < p;
+ *                ids of EQUAL value are kept or dropped together; the largest value always survives
+ *   draw         inverse CDF at u[row] over the surviving ids in ASCENDING id order (torch.multinomial's distribution over the
+ *                filtered softmax); u == NULL: first index of the maximum (torch.argmax) -- greedy with a penalty
+ * Masses are exp(x - rowmax) in 2^-40 fixed point, summed in integers: every result is bit-identical whatever the grid or launch.
+ * No allocation, no host synchronisation: graph-capturable.  Scratch is the caller's `ws` of afhip_sample_filter_workspace_bytes. */
+typedef struct {
+    const float* logits;       /* [rows, ld] f32 */
+    const float* cfg_logits;   /* [rows, ld] f32 or NULL: logits * cfg + cfg_logits * one_minus_cfg (afhip_sample_args' rounding) */
+    float cfg, one_minus_cfg;
+    int model_dtype;           /* AFHIP_BF16: logits and every intermediate of the mix rounded to bf16 (as afhip_sample_args) */
+    int rows, V, ld;           /* V <= ld; V < 2^23 */
+    const int32_t* allowed;    /* [rows][n_iv][2] half-open id intervals or NULL (all ids): ids outside are -inf before any step */
+    int n_iv;                  /* 1..64 when allowed != NULL */
+    const int32_t* penalty_ids;/* [rows, max_ids] ids already in the sequence (any order, repeats allowed; out-of-range ignored) or NULL */
+    const int32_t* n_ids;      /* [rows] device counts of valid entries of penalty_ids (<= max_ids) */
+    int max_ids;
+    float penalty;             /* > 0; 1 = off.  A penalty needs V <= 262144 */
+    float temperature;         /* > 0 */
+    int top_k;                 /* 0 = off, else 1..V */
+    int exact_k;
+    float top_p;               /* (0, 1]; 1 = off */
+    const float* u;            /* [rows] uniforms in [0, 1), or NULL: argmax */
+    float* scores;             /* [rows, ld_scores] out or NULL: the processed row, -inf where removed */
+    int ld_scores;
+    int64_t* token;            /* [rows] out or NULL */
+} afhip_sample_filter_args;
+size_t afhip_sample_filter_workspace_bytes(int rows, int V);
+int afhip_sample_filter(const afhip_sample_filter_args* args, void* ws, size_t ws_bytes, void* stream);
+
 /* One greedy decode step for B sequences entirely on device: embed prev token (stream 0 = token, others pad),
  * forward 1 position, lm_head on stream 0, masked argmax, append to out_tokens[step], update finished flags
  * (eos/eot, lm/parallel.py:503-513).  No host sync. */
