@@ -141,6 +141,7 @@ SIGNATURES = {
     "afhip_sample_filter_workspace_bytes": (_Z, [_I, _I]),
     "afhip_sample_filter": (_I, [C.POINTER(SampleFilterArgs), _P, _Z, _P]),
     "afhip_llm_decode_step": (_I, [C.POINTER(LlmWeights), C.POINTER(KvCache), C.POINTER(DecodeState), _I, _I, _I, _P, _Z, _P]),
+    "afhip_llm_decode_imaged": (_I, [C.POINTER(LlmWeights), _I]),
 }
 
 _lib = None

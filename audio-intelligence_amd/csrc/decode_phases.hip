@@ -202,6 +202,9 @@ bool afhip_decode_phases_supported(const afhip_llm_weights* w, int B) {
     if (H % 512 != 0 || I % 512 != 0 || AO % 512 != 0) return false;
     if (cdiv(H, cus) > 16 || cdiv(qw, cus) > 32 || (2 * I) % 64 != 0 || 2 * I < 8192) return false;
     if ((size_t)16 * 2 * I * 2 >= (1ull << 31) || (size_t)B * qw * 2 >= (1ull << 31)) return false;
+    // e4m3 phases: wave w takes the 128-deep K steps w, w + 8, ... (img_phase.h), so a K below 1024 leaves waves that own no step and never
+    // write their combine partials nor their rows of the sums of squares.  Every phase K (hidden, n_q * hd, inter) must give each wave one.
+    if (w->qkv_w8 != nullptr && (H < 1024 || AO < 1024 || I < 1024)) return false;
     return true;
 }
 

@@ -39,7 +39,8 @@ struct ImgDesc {
 // W8: the weights are OCP e4m3 bytes with one f32 scale per output row (W8A16, gemm_skinny_fp8.hip): a K step is 128 deep so that a lane
 // still reads 32 contiguous bytes of its weight row; the 32 values are widened to bf16 in registers and meet the lane's four A fragments
 // -- chunks of the SAME bf16 image (64-step 2 s + (q >> 1), column group 2 (q & 1) + (c >> 1), half c & 1) -- in four MFMAs.  K / 128 need not
-// divide by the eight waves: wave w takes steps w, w + 8, ... of every unit and all of them meet at the unit's combine barrier.
+// divide by the eight waves: wave w takes steps w, w + 8, ... of every unit and all of them meet at the unit's combine barrier.  That needs
+// K >= 1024 (every wave owns at least one step): afhip_decode_phases_supported sends smaller e4m3 widths to the row-major launches.
 template <int NT, bool PAIR, bool RMS, int RM, int DEPTH, bool W8 = false>
 struct ImgPhase {
     static_assert(RM == 8 || RM == 16, "activation image rows");
@@ -317,7 +318,7 @@ struct ImgPhase {
         for (int g0 = 0; g0 < total; g0 += DEPTH) {
 #pragma unroll
             for (int d = 0; d < DEPTH; ++d) {
-                if (g0 + d < total) {                               // wave-uniform; every wave reaches each unit's combine barrier exactly once
+                if (g0 + d < total) {                               // wave-uniform; with spw >= 1 in every wave (e4m3: K >= 1024, host) every wave reaches each unit's combine barrier exactly once
                     if constexpr (W8) {
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {

@@ -390,6 +390,14 @@ extern "C" int afhip_masked_argmax(const float* logits, int rows, int ld, const 
     return 0;
 }
 
+// the one predicate of the decode step's path: afhip_llm_decode_step dispatches on it, afhip_llm_decode_imaged reports it
+static bool decode_imaged(const afhip_llm_weights* w, int B) {
+    return w->n_kv > 0 && w->n_q / w->n_kv <= 32 && afhip_decode_phases_supported(w, B) &&
+           (w->qkv_w8 == nullptr || (w->o_w8 && w->gu_w8 && w->down_w8 && w->qkv_s && w->o_s && w->gu_s && w->down_s));
+}
+
+extern "C" int afhip_llm_decode_imaged(const afhip_llm_weights* w, int B) { return w && decode_imaged(w, B) ? 1 : 0; }
+
 extern "C" int afhip_llm_decode_step(const afhip_llm_weights* w, afhip_kv_cache* cache, afhip_decode_state* st, int B, int pos,
                                      int step, void* workspace, size_t workspace_bytes, void* stream) {
     AFHIP_CHECK(w && cache && st && workspace, "afhip_llm_decode_step: null pointer");
@@ -415,8 +423,7 @@ extern "C" int afhip_llm_decode_step(const afhip_llm_weights* w, afhip_kv_cache*
     char* am = base + off; off += afhip_masked_argmax_workspace_bytes(B);      // `off` = start of the decode_phases.hip scratch
     int rc;
     AFHIP_CHECK((st->seq_pos == nullptr) == (st->step_counter == nullptr), "afhip_llm_decode_step: seq_pos and step_counter go together");
-    if (w->n_q / w->n_kv <= 32 && afhip_decode_phases_supported(w, B) &&
-        (w->qkv_w8 == nullptr || (w->o_w8 && w->gu_w8 && w->down_w8 && w->qkv_s && w->o_s && w->gu_s && w->down_s))) {
+    if (decode_imaged(w, B)) {
         // bf16 model (bf16 or e4m3 weight copies), B <= 16: the GEMMs of the step are the persistent imaged phases of decode_phases.hip --
         // activations handed from producer to consumer as fragment-order images -- and the attention merge writes the image the o phase reads
         AFHIP_CHECK(pos >= 0 && pos + 1 <= cache->cap && pos + 1 <= w->rope_max_pos && cache->B >= B && cache->k && cache->v,

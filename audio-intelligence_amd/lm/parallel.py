@@ -203,6 +203,7 @@ class ParallelLLM(nn.Module):
         self._ws = None
         self._allowed = {}
         self._allowed_hi = {}
+        self._allowed_host = {}                         # the same intervals on the host: the head_rows check of _greedy_device_loop
         self._fp8_decode = False
         self._fp8_prefill = False
 
@@ -338,6 +339,7 @@ class ParallelLLM(nn.Module):
             self.register_buffer(f"{io_name}_mask", mask[None, None].to(self.device))
         self._allowed = {}
         self._allowed_hi = {}
+        self._allowed_host = {}
 
     def _allowed_intervals(self, name: str):
         """Stream-0 allowed id runs of a mask buffer as a device int32 [n,2] tensor, plus whether every other
@@ -351,6 +353,7 @@ class ParallelLLM(nn.Module):
             pad_only = bool(((~m[1:]).sum(-1) == 1).all() and (~m[1:, 0]).all()) if self.num_stream > 1 else True
             self._allowed[name] = (iv.to(self.device).contiguous(), pad_only)
             self._allowed_hi[name] = int(ends.max()) if len(ends) else 0
+            self._allowed_host[name] = iv
         return self._allowed[name]
 
     def _stream_intervals(self, name: str):
@@ -583,6 +586,9 @@ class ParallelLLM(nn.Module):
         # every allowed id is below head_rows: the step need not stream the lm_head rows behind it (text decode: the 8 x 1025 audio-code
         # rows, lm/parallel.py:557-568)
         head_rows = self._allowed_hi.get(modality, 0)
+        ends = self._allowed_host[modality][:, 1]
+        # the imaged step drops every allowed id at or above head_rows from the argmax (the other path ignores head_rows): a stale value is a bug
+        assert head_rows == 0 or len(ends) == 0 or head_rows >= int(ends.max()), f"head_rows {head_rows} < an allowed interval's end {int(ends.max())}"
         ws = self._workspace(B, 1, cache.cap)
         max_pos = T0 + max_step - 1                      # largest position this loop can append at
 

@@ -490,11 +490,16 @@ typedef struct {
     int32_t* seq_pos;
     int32_t* step_counter;
     /* > 0: every id inside `allowed` is below head_rows, so the step may compute logits for lm_head rows [0, head_rows) only (text decode:
-     * 256 + text vocab of the 160 520 rows, lm/parallel.py:557-568).  0 = all rows. */
+     * 256 + text vocab of the 160 520 rows, lm/parallel.py:557-568).  0 = all rows.  Only the imaged path (afhip_llm_decode_imaged)
+     * reads it; the other path computes every row.  An allowed id at or above head_rows is the caller's error on the imaged path. */
     int head_rows;
 } afhip_decode_state;
 int afhip_llm_decode_step(const afhip_llm_weights* w, afhip_kv_cache* cache, afhip_decode_state* st, int B, int pos,
                           int step, void* workspace, size_t workspace_bytes, void* stream);
+/* 1 when afhip_llm_decode_step(w, ..., B, ...) runs its GEMMs as the persistent imaged phases (bf16 model or its e4m3 copies,
+ * B <= 16, widths decode_phases.hip accepts, option DECODE_IMAGED on), 0 when it takes the row-major launches.  The same predicate
+ * the step dispatches on. */
+int afhip_llm_decode_imaged(const afhip_llm_weights* w, int B);
 
 #ifdef __cplusplus
 }
