@@ -239,3 +239,53 @@ def build_wide_llm(n_layers=2, dtype=torch.bfloat16, device="cuda:0", seed=3, d_
         model._test_pre = ualm_job.UALMPreprocessor(False, {k: v.copy_for_worker() for k, v in ios.items()}, vocab, iv)
         model._test_enc_sd = enc_sd
     return model, sd, cfg, vocab, iv
+
+
+# the LLM widths the float64 reference tests run at: (H, inter, n_q, n_kv)
+LLM_WIDTHS = [(512, 4096, 8, 2), (1024, 4096, 8, 1), (1536, 8704, 12, 2), (2048, 5632, 32, 4), (4096, 4096, 64, 32), (1536, 8960, 12, 2),
+              (896, 4864, 14, 2)]
+
+
+def llm_cfg_at(Hd, I, nq, nkv):
+    """the 2-layer Qwen2 config of build_llm_at at one width"""
+    return dict(hidden_size=Hd, num_hidden_layers=2, num_attention_heads=nq, num_key_value_heads=nkv, intermediate_size=I,
+                rope_theta=1e6, rms_norm_eps=1e-6)
+
+
+def llm_weights_f64(cfg, vocab=2048, seed=3, dtype=torch.bfloat16):
+    """build_llm_at's weights on the CPU (synthetic.synth_tensor, rounded to `dtype` once), held as float64; the LLM's tensors only"""
+    return {n: syn.synth_tensor(n, s, seed).to(dtype).to(torch.float64)
+            for n, s in syn.llm_param_shapes(cfg, vocab, 8, 8) if not n.startswith(("adaptor", "stream"))}
+
+
+def build_llm_at(shape, text_vocab, seed=3, dtype=torch.bfloat16, device="cuda:0"):
+    """build_wide_llm's recipe at `shape` = (H, inter, n_q, n_kv), 2 layers, a `text_vocab`-id text vocabulary: (model on the GPU,
+    float64 CPU state dict of the same `dtype` values (the LLM's tensors only), cfg)"""
+    from audio_intelligence_amd.lm.parallel import ParallelLLM
+    from audio_intelligence_amd import ualm_job
+    Hd, I, nq, nkv = shape
+    cfg = dict(hidden_size=Hd, num_hidden_layers=2, num_attention_heads=nq, num_key_value_heads=nkv, intermediate_size=I,
+               rope_theta=1e6, rms_norm_eps=1e-6, text_vocab=text_vocab)
+    text_io, audio_io = stub_ios(text_vocab)
+    ios = {"text": text_io, "discrete_audio": audio_io, "continuous_audio": stub_continuous(64)}
+    vocab, iv = ualm_job.build_vocabulary(ios)
+    hf = {"architectures": ["Qwen2ForCausalLM"], "hidden_size": Hd, "num_hidden_layers": 2, "num_attention_heads": nq,
+          "num_key_value_heads": nkv, "intermediate_size": I, "rope_theta": 1e6, "rms_norm_eps": 1e-6, "vocab_size": text_vocab}
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    try:
+        with torch.device(device):
+            model = ParallelLLM(hf, ios, vocab, iv)
+    finally:
+        torch.set_default_dtype(old)
+    sd = {}
+    with torch.no_grad():
+        params = dict(model.named_parameters())
+        for name, shp in syn.llm_param_shapes(cfg, len(vocab), 8, 64):
+            t = syn.synth_tensor(name, shp, seed).to(dtype)
+            params[name].copy_(t)
+            if not name.startswith(("adaptor", "stream")):
+                sd[name] = t.to(torch.float64)
+    model.prepare_inference()
+    model.eval()
+    return model, sd, cfg

@@ -73,19 +73,10 @@ def test_decode_ref_masked_argmax_first_index_and_margin():
 
 # ---- tolerances with teeth ----------------------------------------------------------------------------------------------------------------
 
-SHAPES = [(512, 4096, 8, 2), (1024, 4096, 8, 1), (1536, 8704, 12, 2), (2048, 5632, 32, 4), (4096, 4096, 64, 32), (1536, 8960, 12, 2)]
+SHAPES = H.LLM_WIDTHS
 T0 = 37
-
-
-def _cfg(Hd, I, nq, nkv):
-    return dict(hidden_size=Hd, num_hidden_layers=2, num_attention_heads=nq, num_key_value_heads=nkv, intermediate_size=I,
-                rope_theta=1e6, rms_norm_eps=1e-6)
-
-
-def _weights(cfg, vocab=2048, seed=3):
-    """the GPU test's recipe (synthetic.synth_tensor, rounded to bf16 once), held as float64"""
-    return {n: H.syn.synth_tensor(n, s, seed).to(torch.bfloat16).to(F64)
-            for n, s in H.syn.llm_param_shapes(cfg, vocab, 8, 8) if not n.startswith(("adaptor", "stream"))}
+_cfg = H.llm_cfg_at
+_weights = H.llm_weights_f64
 
 
 def _emulate(site, layer, t):

@@ -4,7 +4,7 @@ Each model is the recipe of helpers.build_wide_llm (seeded weights on the CPU, r
 20 000-id text vocabulary.  Every step is judged on its own: the reference reads the device's own cache and previous tokens.  The widths
 reach what the AF3-7B shape does not: few tile rows per unit, idle workgroups, hd 64 in the imaged attention, e4m3 K / 128 = 8 exactly and
 split 2 / 1 over the waves, the predicate's edges; H 512 in W8A16 is sent to the row-major launches (e4m3 K < 1024), and the Qwen2-1.5B
-width (inter 8960, not a multiple of 512) never takes the imaged path.  Tolerances: tests/decode_ref.py (KV bounds, pick_eps)."""
+width (inter 8960, not a multiple of 512) and the Qwen2-0.5B width (H 896) never take the imaged path.  Tolerances: tests/decode_ref.py (KV bounds, pick_eps)."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +27,7 @@ SHAPES = {
     (2048, 5632, 32, 4): (True, True),          # hd 64 imaged attention, TR 8 / 5
     (4096, 4096, 64, 32): (True, True),         # cdiv(H, 256) = 16, cdiv(qw, 256) = 32
     (1536, 8960, 12, 2): (False, False),        # Qwen2-1.5B: 8960 % 512 != 0
+    (896, 4864, 14, 2): (False, False),         # Qwen2-0.5B: H % 512 != 0, q|k|v 1152, hd 64
 }
 # >= 6 sorted disjoint intervals: single ids, one across the 64-row lm_head unit boundary at 128, the last end not a multiple of 64
 INTERVALS = [[3, 4], [7, 8], [100, 130], [300, 2000], [2500, 9000], [12000, 20131]]
@@ -50,43 +51,11 @@ def _imaged_on():
         _opt("DECODE_IMAGED", 1)
 
 
-def _build(shape, seed=3):
-    """helpers.build_wide_llm's recipe at `shape`: (model on the GPU, float64 CPU state dict of the same bf16 values, cfg)"""
-    from audio_intelligence_amd.lm.parallel import ParallelLLM
-    from audio_intelligence_amd import ualm_job
-    Hd, I, nq, nkv = shape
-    cfg = dict(hidden_size=Hd, num_hidden_layers=2, num_attention_heads=nq, num_key_value_heads=nkv, intermediate_size=I,
-               rope_theta=1e6, rms_norm_eps=1e-6, text_vocab=TEXT_VOCAB)
-    text_io, audio_io = H.stub_ios(TEXT_VOCAB)
-    ios = {"text": text_io, "discrete_audio": audio_io, "continuous_audio": H.stub_continuous(64)}
-    vocab, iv = ualm_job.build_vocabulary(ios)
-    hf = {"architectures": ["Qwen2ForCausalLM"], "hidden_size": Hd, "num_hidden_layers": 2, "num_attention_heads": nq,
-          "num_key_value_heads": nkv, "intermediate_size": I, "rope_theta": 1e6, "rms_norm_eps": 1e-6, "vocab_size": TEXT_VOCAB}
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(torch.bfloat16)
-    try:
-        with torch.device(DEV):
-            model = ParallelLLM(hf, ios, vocab, iv)
-    finally:
-        torch.set_default_dtype(old)
-    sd = {}
-    with torch.no_grad():
-        params = dict(model.named_parameters())
-        for name, shp in H.syn.llm_param_shapes(cfg, len(vocab), 8, 64):
-            t = H.syn.synth_tensor(name, shp, seed).to(torch.bfloat16)
-            params[name].copy_(t)
-            if not name.startswith(("adaptor", "stream")):
-                sd[name] = t.to(torch.float64)
-    model.prepare_inference()
-    model.eval()
-    return model, sd, cfg
-
-
 @pytest.fixture(scope="module", params=list(SHAPES), ids=lambda s: "H%d_I%d_q%d_kv%d" % s)
 def wide(request):
     _need_gpu()
     torch.set_num_threads(H.cpu_threads())
-    model, sd, cfg = _build(request.param)
+    model, sd, cfg = H.build_llm_at(request.param, TEXT_VOCAB)
     refs = {"bf16": sd}
     yield request.param, model, refs, cfg
     del model, refs
