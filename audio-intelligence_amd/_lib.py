@@ -99,6 +99,10 @@ class SampleFilterArgs(C.Structure):
                 ("u", C.c_void_p), ("scores", C.c_void_p), ("ld_scores", C.c_int), ("token", C.c_void_p)]
 
 
+# afhip_encoder_path flags (include/afhip.h)
+ENC_FOLDED, ENC_E4M3, ENC_ATT_STATIC, ENC_FC2_STATIC, ENC_ATTN_ENC64, ENC_ATTN_LAG, ENC_MASK_SHIFT = 1, 2, 4, 8, 16, 32, 8
+
+
 # name -> (restype, argtypes); mirrors include/afhip.h one to one (tests/test_cabi.py checks the header against this)
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -131,6 +135,7 @@ SIGNATURES = {
     "afhip_encoder_workspace_bytes": (_Z, [C.POINTER(EncoderWeights), _I]),
     "afhip_encoder_forward": (_I, [C.POINTER(EncoderWeights), _P, _P, _I, _P, _P, _I, _P, _Z, _P]),
     "afhip_encoder_forward_ragged": (_I, [C.POINTER(EncoderWeights), _P, _P, _P, _I, _P, _P, _Z, _P]),
+    "afhip_encoder_path": (_I, [C.POINTER(EncoderWeights), _I, C.POINTER(_I)]),
     "afhip_llm_workspace_bytes": (_Z, [C.POINTER(LlmWeights), _I, _I, _I]),
     "afhip_llm_forward": (_I, [C.POINTER(LlmWeights), _P, _I, _I, _I, C.POINTER(KvCache), _P, _P, _Z, _P]),
     "afhip_llm_forward_ragged": (_I, [C.POINTER(LlmWeights), _P, _I, _P, _I, C.POINTER(KvCache), _P, _P, _Z, _P]),

@@ -897,6 +897,21 @@ __global__ __launch_bounds__(256) void attn_decode128_kernel(AttnP p_in) {
 }  // namespace
 
 bool afhip_attention_enc64(const afhip_attn_args* a, hipStream_t s);   // attention_enc.hip: the one-wave-per-SIMD encoder form
+bool afhip_attention_enc64_applies(const afhip_attn_args* a);
+
+namespace {
+// the lagged-maximum softmax form of attn_kernel (encoder, LayerNorm-folded mode)
+bool attn_lag_form(const afhip_attn_args* a) {
+    return a->dtype == AFHIP_BF16 && a->hd == 64 && a->q_prescaled && a->key_split == 0 && afhip_opt(AFHIP_OPT_ATTN_NBUF) != 1 &&
+           afhip_opt(AFHIP_OPT_ATTN_LAG) != 0;
+}
+}  // namespace
+
+// which kernel afhip_attention(a) runs for a non-decode shape: the predicates it dispatches on (common.h)
+int afhip_attention_form(const afhip_attn_args* a) {
+    if (afhip_attention_enc64_applies(a)) return AFHIP_ENC_ATTN_ENC64;
+    return attn_lag_form(a) ? AFHIP_ENC_ATTN_LAG : 0;
+}
 
 extern "C" int afhip_attention(const afhip_attn_args* a, void* stream) {
     AFHIP_CHECK(a != nullptr, "afhip_attention: null args");
@@ -1001,8 +1016,7 @@ extern "C" int afhip_attention(const afhip_attn_args* a, void* stream) {
         if (nbuf == 2) hipLaunchKernelGGL((attn_kernel<TT, HH, 2>), grid, block, lds, s, p);             \
         else hipLaunchKernelGGL((attn_kernel<TT, HH, 1>), grid, block, lds, s, p);                        \
     } while (0)
-    const int lag = afhip_opt(AFHIP_OPT_ATTN_LAG) != 0;   // A/B switch
-    if (a->dtype == AFHIP_BF16 && a->hd == 64 && a->q_prescaled && a->key_split == 0 && nbuf == 2 && lag) {
+    if (attn_lag_form(a)) {                                                                 // A/B switch ATTN_LAG
         hipLaunchKernelGGL((attn_kernel<bf16, 64, 2, true>), grid, block, lds, s, p);      // lagged-maximum softmax (encoder, LayerNorm-folded mode)
     } else if (a->dtype == AFHIP_BF16) {
         if (a->hd == 64) AFHIP_ATTN_LAUNCH(bf16, 64); else AFHIP_ATTN_LAUNCH(bf16, 128);

@@ -562,12 +562,18 @@ __global__ __launch_bounds__(256, 1) void attn_enc64_kernel(EncAttnP p) {
 
 }  // namespace
 
-// Called by afhip_attention (attention.hip) for the shape this form covers; returns false when it does not apply.
-bool afhip_attention_enc64(const afhip_attn_args* a, hipStream_t s) {
+// The shapes this form covers (afhip_attention dispatches on it, afhip_encoder_path reports it); reads no tensor.
+bool afhip_attention_enc64_applies(const afhip_attn_args* a) {
     if (!afhip_opt(AFHIP_OPT_ATTN_ENC64)) return false;   // A/B switch
     if (a->dtype != AFHIP_BF16 || a->hd != 64 || !a->q_prescaled || a->causal || a->key_split > 0 || a->n_q != a->n_kv || a->Tq != a->Tk) return false;
     if (a->new_k || a->seq_pos) return false;
     if ((long long)a->Tk * a->ld_kv * 2 >= (1ll << 31) || (long long)a->Tq * a->ld_q * 2 >= (1ll << 31)) return false;      // 32-bit DMA offsets inside one (clip, head), K / V and Q
+    return (long long)cdiv(a->Tq, E_QT) * a->n_q * a->B < (1ll << 31);
+}
+
+// Called by afhip_attention (attention.hip) for the shape this form covers; returns false when it does not apply.
+bool afhip_attention_enc64(const afhip_attn_args* a, hipStream_t s) {
+    if (!afhip_attention_enc64_applies(a)) return false;
     EncAttnP p;
     p.q = (const char*)a->q; p.k = (const char*)a->k; p.v = (const char*)a->v; p.o = (char*)a->out;
     p.key_len = a->key_len; p.row_off = a->row_off;
@@ -577,7 +583,6 @@ bool afhip_attention_enc64(const afhip_attn_args* a, hipStream_t s) {
     p.q_hs = a->q_head_stride; p.kv_hs = a->kv_head_stride; p.o_hs = a->o_head_stride > 0 ? a->o_head_stride : a->hd;
     p.n_qt = cdiv(a->Tq, E_QT);
     const long long nblk = (long long)p.n_qt * a->n_q * a->B;
-    if (nblk >= (1ll << 31)) return false;
     p.n_blk = (int)nblk;
     p.out_fp8 = a->out_fp8; p.out_inv = a->out_scale_inv;
 #ifdef AFHIP_ENC_STAMPS

@@ -10,8 +10,58 @@
 #include <stdlib.h>
 
 bool gemm_pp_available();   // gemm_pp.hip
+int afhip_attention_form(const afhip_attn_args* a);   // attention.hip: AFHIP_ENC_ATTN_ENC64 / AFHIP_ENC_ATTN_LAG / 0 (generic)
 
 namespace {
+
+// The forward's arithmetic, decided once per call from the weights, the batch and the options: encoder_forward_impl dispatches on these
+// predicates and afhip_encoder_path reports them.
+struct EncPath {
+    bool fold;      // LayerNorm-folded q|k|v and fc1 (bf16 throughput mode)
+    bool f8;        // e4m3-operand mode
+    int mask;       // ... its projections (bit 0 qkv, 1 out, 2 fc1, 3 fc2)
+    bool qkv_fold;  // ... with q|k|v LayerNorm-folded
+};
+
+EncPath enc_path(const afhip_encoder_weights* w, int B) {
+    EncPath p;
+    const int d = w->d_model, f = w->ffn_dim;
+    p.fold = w->dtype == AFHIP_BF16 && w->qkv_wf && w->qkv_cs && w->qkv_bf && w->fc1_wf && w->fc1_cs && w->fc1_bf &&
+             B * w->max_pos >= 512 && d % 256 == 0 && f % 256 == 0 && gemm_pp_available();    // decided on the PADDED row count: the packed
+                                                                                                // forward must take the same arithmetic
+    p.f8 = w->dtype == AFHIP_BF16 && w->qkv_w8 && w->qkv_s8 && w->out_w8 && w->out_s8 && w->fc1_w8 && w->fc1_s8 && w->fc2_w8 && w->fc2_s8 &&
+           d % 256 == 0 && f % 256 == 0;
+    p.mask = p.f8 ? (afhip_opt(AFHIP_OPT_FP8_MASK) | (afhip_opt(AFHIP_OPT_FP8_FC2) ? 8 : 0)) : 0;
+    p.qkv_fold = p.f8 && !(p.mask & 1) && !(p.mask & 8) && p.fold;
+    return p;
+}
+
+// q leaves the q|k|v GEMM prescaled (afhip_attn_args.q_prescaled)
+bool enc_q_prescaled(const afhip_encoder_weights* w, const EncPath& p) {
+    return (p.f8 ? p.qkv_fold : p.fold) && w->q_prescaled;
+}
+
+// layer l's attention output statically quantised (afhip_encoder_weights.att_out_scale) / fc2's input (fc2_in_scale)
+bool enc_att_static(const afhip_encoder_weights* w, const EncPath& p, int l) {
+    return p.f8 && (p.mask & 2) && enc_q_prescaled(w, p) && w->d_model / w->n_heads == 64 && w->att_out_scale && w->att_out_scale[l] > 0.f;
+}
+bool enc_fc2_static(const afhip_encoder_weights* w, const EncPath& p, int l) {
+    return p.f8 && (p.mask & 4) && !(p.mask & 8) && w->fc2_in_scale && w->fc2_in_scale[l] > 0.f;
+}
+
+// the attention arguments of every layer (tensor pointers left to the caller)
+afhip_attn_args enc_attn_args(const afhip_encoder_weights* w, const EncPath& p, int B) {
+    const int d = w->d_model, Tp = w->max_pos, hd = d / w->n_heads;
+    afhip_attn_args a = {};
+    a.B = B; a.Tq = Tp; a.Tk = Tp; a.n_q = w->n_heads; a.n_kv = w->n_heads; a.hd = hd;
+    a.ld_q = 3 * d; a.ld_kv = 3 * d; a.ld_o = d;
+    a.q_batch_stride = (long long)Tp * 3 * d; a.kv_batch_stride = (long long)Tp * 3 * d; a.o_batch_stride = (long long)Tp * d;
+    a.q_head_stride = hd; a.kv_head_stride = hd;
+    a.o_head_stride = 0; a.key_split = 0; a.partial_ws = nullptr; a.partial_ws_bytes = 0;
+    a.causal = 0; a.q_pos0 = 0; a.scale = 1.0f / sqrtf((float)hd); a.dtype = w->dtype;
+    a.q_prescaled = enc_q_prescaled(w, p) ? 1 : 0;
+    return a;
+}
 
 struct EncWs {
     char* h;     // [B*Tp, d]
@@ -142,36 +192,26 @@ int encoder_forward_impl(const afhip_encoder_weights* w, const void* mel_btc, co
     // LayerNorm-folded mode (bf16, ping-pong-GEMM shapes): the two LayerNorms of a layer never write a normalised copy of the
     // stream.  out-proj / fc2 emit row (sum, sum of squares) partials of what they store, a 3-us finalize turns them into
     // (mean, rstd), and q/k/v / fc1 run on the RAW stream with gamma folded into their weights (afhip.h).
-    const bool fold = dt == AFHIP_BF16 && w->qkv_wf && w->qkv_cs && w->qkv_bf && w->fc1_wf && w->fc1_cs && w->fc1_bf &&
-                      B * Tp >= 512 && d % 256 == 0 && f % 256 == 0 && gemm_pp_available();      // decided on the PADDED row count: the packed
-                                                                                               // forward must take the same arithmetic
-    const int P = d / 64;
     // e4m3-operand mode (BASELINE config 5): explicit LayerNorm fused into the per-row quantisation pass, four fp8 GEMMs per layer
-    const bool f8 = dt == AFHIP_BF16 && w->qkv_w8 && w->qkv_s8 && w->out_w8 && w->out_s8 && w->fc1_w8 && w->fc1_s8 && w->fc2_w8 && w->fc2_s8 &&
-                    d % 256 == 0 && f % 256 == 0;
+    const EncPath path = enc_path(w, B);
+    const bool fold = path.fold, f8 = path.f8;
+    const int P = d / 64;
     for (int l = 0; l < w->n_layers; ++l) {
-        afhip_attn_args a = {};
+        afhip_attn_args a = enc_attn_args(w, path, B);
         a.q = ws.qkv; a.k = ws.qkv + (size_t)d * sz; a.v = ws.qkv + (size_t)2 * d * sz; a.out = att;
         a.key_len = feat_len;
         a.row_off = ragged ? ws.roff : nullptr;
-        a.B = B; a.Tq = Tp; a.Tk = Tp; a.n_q = w->n_heads; a.n_kv = w->n_heads; a.hd = hd;
-        a.ld_q = 3 * d; a.ld_kv = 3 * d; a.ld_o = d;
-        a.q_batch_stride = (long long)Tp * 3 * d; a.kv_batch_stride = (long long)Tp * 3 * d; a.o_batch_stride = (long long)Tp * d;
-        a.q_head_stride = hd; a.kv_head_stride = hd;
-        a.o_head_stride = 0; a.key_split = 0; a.partial_ws = nullptr; a.partial_ws_bytes = 0;
-        a.causal = 0; a.q_pos0 = 0; a.scale = 1.0f / sqrtf((float)hd); a.dtype = dt;
-        a.q_prescaled = (fold && !f8 && w->q_prescaled) ? 1 : 0;
         if (f8) {
             float* sc = ws.stats;                           // [rows] row scales of the activation being multiplied
             // which projections take e4m3 operands: bit 0 qkv, 1 out, 2 fc1, 3 fc2 (AFHIP_FP8_MASK; the rest run the plain bf16 GEMM
             // behind an explicit LayerNorm).  Default 6 = out + fc1: q / k / v stay bf16 because the softmax amplifies e4m3 noise on
             // its logits more than anything downstream -- measured through the LLM (tests/test_gpu_config5.py, 10 clips x 32 steps):
             // mask 7 (qkv too) 284-289 of 320 tokens equal to the bf16 run, mask 6 296, mask 14 (+ fc2) 294, mask 15 285
-            const int mask = afhip_opt(AFHIP_OPT_FP8_MASK) | (afhip_opt(AFHIP_OPT_FP8_FC2) ? 8 : 0);
+            const int mask = path.mask;
             // q | k | v in bf16: the LayerNorm-folded GEMM over the raw stream when the folded weights exist (row statistics from the
             // conv stem / the previous layer's bf16 fc2 epilogue, exactly as in the bf16 mode; q leaves prescaled for the encoder
             // attention kernel), else an explicit LayerNorm + the plain GEMM
-            const bool qkv_fold = !(mask & 1) && !(mask & 8) && fold;
+            const bool qkv_fold = path.qkv_fold;
             if (mask & 1) {
                 if ((rc = afhip_quant_rows(h, d, w->ln1_w[l], w->ln1_b[l], 1e-5f, 1, ws.ln, sc, rows, d, s))) return rc;
                 if ((rc = gemm8(ws.ln, sc, w->qkv_w8[l], w->qkv_s8[l], w->qkv_b[l], nullptr, ws.qkv, rows, 3 * d, d, 3 * d, 0, AFHIP_ACT_NONE, s))) return rc;
@@ -180,7 +220,6 @@ int encoder_forward_impl(const afhip_encoder_weights* w, const void* mel_btc, co
                 if (l == 0 && (rc = afhip_row_stats(h, rows, d, 1e-5f, dt, st, s))) return rc;
                 if ((rc = gemm(h, w->qkv_wf[l], nullptr, nullptr, ws.qkv, rows, 3 * d, d, d, 3 * d, 0, dt, AFHIP_ACT_NONE, 0, s, 0, 0, 0, 0,
                                st, w->qkv_cs[l], w->qkv_bf[l], nullptr))) return rc;
-                a.q_prescaled = w->q_prescaled ? 1 : 0;
             } else {
                 if ((rc = afhip_layernorm(h, w->ln1_w[l], w->ln1_b[l], ws.ln, rows, d, 1e-5f, dt, s))) return rc;
                 if ((rc = gemm(ws.ln, w->qkv_w[l], w->qkv_b[l], nullptr, ws.qkv, rows, 3 * d, d, d, 3 * d, 0, dt, AFHIP_ACT_NONE, 0, s))) return rc;
@@ -188,7 +227,7 @@ int encoder_forward_impl(const afhip_encoder_weights* w, const void* mel_btc, co
             // attention output statically quantised (afhip_encoder_weights.att_out_scale): the attention kernel writes e4m3 bytes into `att`
             // and the out-projection reads them with one scale for every row -- no bf16 round trip, no quantisation launch.  Needs the
             // encoder attention form, i.e. the prescaled q of the LayerNorm-folded q | k | v GEMM
-            const bool att_static = (mask & 2) && a.q_prescaled && hd == 64 && w->att_out_scale && w->att_out_scale[l] > 0.f;
+            const bool att_static = enc_att_static(w, path, l);
             if (att_static) { a.out_fp8 = 1; a.out_scale_inv = 1.0f / w->att_out_scale[l]; }
             if ((rc = afhip_attention(&a, s))) return rc;
             if (w->calib_amax && !att_static && (rc = afhip_absmax_bf16(att, (long long)rows * d, w->calib_amax + w->n_layers + l, s))) return rc;
@@ -202,7 +241,7 @@ int encoder_forward_impl(const afhip_encoder_weights* w, const void* mel_btc, co
             }
             // fc2's input statically quantised (afhip_encoder_weights.fc2_in_scale): fc1's epilogue writes the GELU output as e4m3 bytes into
             // ws.big and fc2 reads them with one scale for every row -- no [rows, ffn] bf16 round trip and no quantisation launch
-            const bool fc2_static = (mask & 4) && !(mask & 8) && w->fc2_in_scale && w->fc2_in_scale[l] > 0.f;
+            const bool fc2_static = enc_fc2_static(w, path, l);
             if (mask & 4) {
                 if ((rc = afhip_quant_rows(h, d, w->ln2_w[l], w->ln2_b[l], 1e-5f, 1, ws.ln, sc, rows, d, s))) return rc;
                 if (fc2_static) {
@@ -268,6 +307,22 @@ int encoder_forward_impl(const afhip_encoder_weights* w, const void* mel_btc, co
     return afhip_avgpool_ln(h, w->lnf_w, w->lnf_b, out, B, Tp / 2, d, 1e-5f, dt, s);
 }
 }  // namespace
+
+extern "C" int afhip_encoder_path(const afhip_encoder_weights* w, int B, int* flags) {
+    AFHIP_CHECK(w && flags, "afhip_encoder_path: null pointer");
+    AFHIP_CHECK(B > 0, "afhip_encoder_path: bad batch %d", B);
+    AFHIP_CHECK(w->d_model > 0 && w->n_heads > 0 && w->d_model % w->n_heads == 0 && w->max_pos > 0 && w->n_layers >= 0,
+                "afhip_encoder_path: bad config");
+    const EncPath p = enc_path(w, B);
+    int fl = (p.fold ? AFHIP_ENC_FOLDED : 0) | (p.f8 ? AFHIP_ENC_E4M3 | (p.mask << AFHIP_ENC_MASK_SHIFT) : 0);
+    for (int l = 0; l < w->n_layers; ++l) {
+        if (enc_att_static(w, p, l)) fl |= AFHIP_ENC_ATT_STATIC;
+        if (enc_fc2_static(w, p, l)) fl |= AFHIP_ENC_FC2_STATIC;
+    }
+    const afhip_attn_args a = enc_attn_args(w, p, B);
+    *flags = fl | afhip_attention_form(&a);
+    return 0;
+}
 
 extern "C" int afhip_encoder_forward(const afhip_encoder_weights* w, const void* mel_btc, const int32_t* feat_len, int B,
                                      void* out, void* hidden_out, int hidden_layer, void* workspace, size_t workspace_bytes,

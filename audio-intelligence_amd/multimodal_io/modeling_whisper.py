@@ -324,8 +324,19 @@ class AFWhisperEncoder(nn.Module):
                 keep.append(self._calib)
                 w.calib_amax = self._calib.data_ptr()
         from .. import torch_ops
-        self._packed = SimpleNamespace(w=w, keep=keep, arrays=arrays, blob=torch_ops.weights_blob(w))
+        self._packed = SimpleNamespace(w=w, keep=keep, arrays=arrays, blob=torch_ops.weights_blob(w),
+                                       f8={n: lists[n] for n in fold_names if n.endswith(("_w8", "_s8"))})
         return self._packed
+
+    def path(self, B: int) -> dict:
+        """The arithmetic a forward of B clips takes (afhip_encoder_path, the predicates the forward dispatches on): folded, e4m3, mask,
+        att_static, fc2_static and attention ("enc64", "lag" or "generic")."""
+        fl = C.c_int(0)
+        L.check(L.lib().afhip_encoder_path(C.byref(self.pack().w), int(B), C.byref(fl)))
+        f = fl.value
+        return dict(folded=bool(f & L.ENC_FOLDED), e4m3=bool(f & L.ENC_E4M3), mask=(f >> L.ENC_MASK_SHIFT) & 15,
+                    att_static=bool(f & L.ENC_ATT_STATIC), fc2_static=bool(f & L.ENC_FC2_STATIC),
+                    attention="enc64" if f & L.ENC_ATTN_ENC64 else "lag" if f & L.ENC_ATTN_LAG else "generic")
 
     def _workspace(self, B: int) -> torch.Tensor:
         lib = L.lib()

@@ -340,6 +340,15 @@ int afhip_encoder_forward(const afhip_encoder_weights* w, const void* mel_btc, c
  * 0 <= feat_len[b] <= max_pos.  Workspace as afhip_encoder_workspace_bytes(w, B). */
 int afhip_encoder_forward_ragged(const afhip_encoder_weights* w, const void* mel_btc, const int32_t* feat_len, const int32_t* feat_len_host,
                                  int B, void* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The arithmetic afhip_encoder_forward(w, ..., B, ...) and its ragged form take, from the predicates they dispatch on: *flags = an OR of
+ * AFHIP_ENC_* -- LayerNorm-folded q|k|v / fc1, e4m3 operands (the mask in effect in bits AFHIP_ENC_MASK_SHIFT.., bit 0 qkv, 1 out, 2 fc1,
+ * 3 fc2), statically quantised attention output / fc2 input (in some layer), and the attention kernel (ENC64: attention_enc.hip; LAG:
+ * the lagged-maximum form of the generic kernel; neither: the generic kernel).  Reads no tensor. */
+enum {
+    AFHIP_ENC_FOLDED = 1, AFHIP_ENC_E4M3 = 2, AFHIP_ENC_ATT_STATIC = 4, AFHIP_ENC_FC2_STATIC = 8,
+    AFHIP_ENC_ATTN_ENC64 = 16, AFHIP_ENC_ATTN_LAG = 32, AFHIP_ENC_MASK_SHIFT = 8
+};
+int afhip_encoder_path(const afhip_encoder_weights* w, int B, int* flags);
 
 /* ---------------------------------------------------------------------------------------------
  * LLM (Qwen2 decoder stack + UALM head).  Replaces ParallelLLM._step (lm/parallel.py:570-597) over

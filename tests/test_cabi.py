@@ -141,3 +141,25 @@ def test_no_kernel_spills_and_no_flat_memory_instruction():
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "check_spills.py")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "kernels checked" in r.stdout
+
+
+def test_encoder_path_reports_the_forward_predicates():
+    """afhip_encoder_path on the host: the flag constants of _lib match the header; a bf16 model without folded or e4m3 copies runs
+    explicit with the generic attention; with folded copies (pointers only: the predicate reads no tensor) at 512 padded rows it runs
+    folded with the hd-64 encoder attention, below 512 rows explicit; null arguments fail with an error code"""
+    from audio_intelligence_amd import _lib as L
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in ("FOLDED", "E4M3", "ATT_STATIC", "FC2_STATIC", "ATTN_ENC64", "ATTN_LAG", "MASK_SHIFT"):
+        assert int(re.search(r"AFHIP_ENC_%s\s*=\s*(\d+)" % name, src).group(1)) == getattr(L, "ENC_" + name), name
+    lib = L.load_library()
+    w = L.EncoderWeights()
+    w.n_mels, w.d_model, w.n_heads, w.ffn_dim, w.n_layers, w.max_pos, w.dtype = 128, 512, 8, 2048, 2, 250, L.dtype_code(__import__("torch").bfloat16)
+    fl = C.c_int(-1)
+    assert lib.afhip_encoder_path(C.byref(w), 3, C.byref(fl)) == 0 and fl.value == 0
+    dummy = (C.c_void_p * 2)(1, 1)
+    for n in ("qkv_wf", "qkv_cs", "qkv_bf", "fc1_wf", "fc1_cs", "fc1_bf"):
+        setattr(w, n, C.cast(dummy, L.c_void_pp))
+    w.q_prescaled = 1
+    assert lib.afhip_encoder_path(C.byref(w), 3, C.byref(fl)) == 0 and fl.value == L.ENC_FOLDED | L.ENC_ATTN_ENC64
+    assert lib.afhip_encoder_path(C.byref(w), 1, C.byref(fl)) == 0 and fl.value == 0
+    assert lib.afhip_encoder_path(None, 1, C.byref(fl)) != 0 and lib.afhip_encoder_path(C.byref(w), 1, None) != 0
