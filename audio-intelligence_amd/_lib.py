@@ -99,6 +99,12 @@ class SampleFilterArgs(C.Structure):
                 ("u", C.c_void_p), ("scores", C.c_void_p), ("ld_scores", C.c_int), ("token", C.c_void_p)]
 
 
+class BeamSelectArgs(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("model_dtype", C.c_int), ("B", C.c_int), ("nb", C.c_int), ("V", C.c_int), ("ld", C.c_int),
+                ("running", C.c_void_p), ("K", C.c_int), ("values", C.c_void_p), ("indices", C.c_void_p), ("scores", C.c_void_p),
+                ("ld_scores", C.c_int)]
+
+
 # afhip_encoder_path flags (include/afhip.h)
 ENC_FOLDED, ENC_E4M3, ENC_ATT_STATIC, ENC_FC2_STATIC, ENC_ATTN_ENC64, ENC_ATTN_LAG, ENC_MASK_SHIFT = 1, 2, 4, 8, 16, 32, 8
 
@@ -145,6 +151,10 @@ SIGNATURES = {
     "afhip_sample_topk": (_I, [C.POINTER(SampleArgs), _P]),
     "afhip_sample_filter_workspace_bytes": (_Z, [_I, _I]),
     "afhip_sample_filter": (_I, [C.POINTER(SampleFilterArgs), _P, _Z, _P]),
+    "afhip_beam_select_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "afhip_beam_select": (_I, [C.POINTER(BeamSelectArgs), _P, _Z, _P]),
+    "afhip_kv_gather_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "afhip_kv_gather": (_I, [C.POINTER(KvCache), C.POINTER(KvCache), _I, _I, _I, _I, _P, _P, _P, _I, _P, _Z, _P]),
     "afhip_llm_decode_step": (_I, [C.POINTER(LlmWeights), C.POINTER(KvCache), C.POINTER(DecodeState), _I, _I, _I, _P, _Z, _P]),
     "afhip_llm_decode_imaged": (_I, [C.POINTER(LlmWeights), _I]),
 }

@@ -77,6 +77,44 @@ def _generation_knobs(generation_config, kwargs, **explicit) -> dict:
     return out
 
 
+# beam-search knobs (GenerationMixin._beam_search) and the values under which they ask for nothing
+_BEAM_NEUTRAL = {"num_beams": 1, "num_return_sequences": 1, "length_penalty": 1.0, "early_stopping": False}
+
+
+def _beam_knobs(generation_config, kwargs, do_sample=None):
+    """Peels the beam-search knobs off `kwargs` / `generation_config` (explicit kwargs win).  Returns (beam, generation_config,
+    kwargs): `beam` is None -- and the inputs come back unchanged, so `_generation_knobs` judges them as before -- unless
+    num_beams > 1 without sampling; then `beam` holds num_beams / num_return_sequences / length_penalty / early_stopping and the
+    returned config and kwargs carry the neutral values of those four."""
+    if generation_config is None:
+        base = {}
+    elif isinstance(generation_config, dict):
+        base = dict(generation_config)
+    elif hasattr(generation_config, "to_dict"):
+        base = generation_config.to_dict()
+    else:
+        base = dict(vars(generation_config))
+    merged = {**base, **{k: v for k, v in kwargs.items() if k in _BEAM_NEUTRAL}}
+    nb = merged.get("num_beams")
+    sampling = do_sample if do_sample is not None else kwargs.get("do_sample", base.get("do_sample"))
+    if nb is None or nb <= 1 or sampling:
+        return None, generation_config, kwargs
+    beam = {k: (merged[k] if merged.get(k) is not None else v) for k, v in _BEAM_NEUTRAL.items()}
+    beam["num_beams"] = int(nb)
+    beam["num_return_sequences"] = int(beam["num_return_sequences"])
+    beam["length_penalty"] = float(beam["length_penalty"])
+    if beam["early_stopping"] not in (True, False, "never"):
+        raise ValueError(f"`early_stopping` must be True, False or 'never', got {beam['early_stopping']!r}")
+    if beam["num_return_sequences"] > beam["num_beams"]:
+        raise ValueError("`num_return_sequences` has to be smaller or equal to `num_beams`.")
+    return beam, {**base, **_BEAM_NEUTRAL}, {k: v for k, v in kwargs.items() if k not in _BEAM_NEUTRAL}
+
+
+def _gather_beams(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """t [B, n, ...], idx [B, k] -> t[b, idx[b, j], ...] (GenerationMixin._gather_beams)"""
+    return torch.take_along_dim(t, idx.view(idx.shape + (1,) * (t.dim() - 2)), dim=1)
+
+
 class _CausalLM(nn.Module):
     """`Qwen2ForCausalLM` parameter layout: `model.embed_tokens / layers / norm` + `lm_head` (no bias)."""
 
@@ -335,7 +373,12 @@ class Qwen2AudioForConditionalGeneration(nn.Module):
         set raises NotImplementedError.  The processors and the draw run in one HIP kernel (afhip_sample_filter); the draw takes one
         `torch.rand(B, generator=generator)` per step (`generator` is an extension: a fixed seed gives a fixed token stream).
         `return_dict_in_generate=True` returns a namespace with `sequences`, and `scores` (processed rows, `output_scores`) / `logits`
-        (raw rows, `output_logits`) as tuples of [B, V] f32 per step."""
+        (raw rows, `output_logits`) as tuples of [B, V] f32 per step.
+
+        Beam search (GenerationMixin._beam_search): `num_beams` > 1 without sampling, with `num_return_sequences` (<= num_beams),
+        `length_penalty` and `early_stopping` (True, False, "never"); see `_generate_beam`.  Beam sampling and a repetition
+        penalty under beams raise NotImplementedError."""
+        beam, generation_config, kwargs = _beam_knobs(generation_config, kwargs, do_sample)
         cfg = _generation_knobs(generation_config, kwargs, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                 do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                 return_dict_in_generate=return_dict_in_generate, output_scores=output_scores, output_logits=output_logits)
@@ -343,6 +386,10 @@ class Qwen2AudioForConditionalGeneration(nn.Module):
         if max_new is None:
             max_new = cfg["max_length"] - input_ids.shape[1] if cfg.get("max_length") is not None else 20
         rp = cfg.get("repetition_penalty")
+        if beam is not None:
+            if rp not in (None, 1.0):
+                raise NotImplementedError("generate(): `repetition_penalty` is not supported with num_beams > 1")
+            return self._generate_beam(input_ids, input_features, attention_mask, feature_attention_mask, max_new, cfg, beam)
         sampling = bool(cfg.get("do_sample"))
         want_dict = bool(cfg.get("return_dict_in_generate"))
         if not sampling and rp in (None, 1.0) and not want_dict:
@@ -419,6 +466,118 @@ class Qwen2AudioForConditionalGeneration(nn.Module):
             return seqs
         return SimpleNamespace(sequences=seqs, scores=tuple(scores) if out_scores else None, logits=tuple(raw) if out_logits else None,
                                attentions=None, hidden_states=None, past_key_values=None)
+
+    @torch.no_grad()
+    def _generate_beam(self, input_ids, input_features, attention_mask, feature_attention_mask, max_new_tokens, cfg, beam):
+        """Beam search with GenerationMixin._beam_search's semantics (steps b-g, finalisation and cropping).  The audio tower and the
+        prefill run once for the B prompts; the cache is then expanded to B * num_beams slots by afhip_kv_gather.  Per step,
+        afhip_beam_select picks the top max(2, 1 + n_eos) * num_beams continuations of each prompt, HF's bookkeeping runs as small
+        device tensor ops, afhip_kv_gather reorders the generated rows of the cache in place, and the ragged decode feeds the selected
+        tokens.  The prompt width W of `input_ids` is HF's decoder_prompt_len: max_length = W + max_new_tokens."""
+        from ..lm.parallel import KVCache
+        lib = L.lib()
+        dev = self.device
+        nb, nrs, lp, es = beam["num_beams"], beam["num_return_sequences"], beam["length_penalty"], beam["early_stopping"]
+        if max_new_tokens < 1:
+            raise ValueError("beam search needs max_new_tokens >= 1")
+        eos, pad = self._eos_pad(cfg.get("eos_token_id"), cfg.get("pad_token_id"))
+        out_scores, out_logits = bool(cfg.get("output_scores")), bool(cfg.get("output_logits"))
+        V = self.vocab_size
+        input_ids = input_ids.to(dev)
+        B, W = input_ids.shape
+        R = B * nb
+        max_length = W + max_new_tokens
+        hid, cache0, _, _, _, _ = self._prefill(input_ids, input_features, attention_mask, feature_attention_mask, None, None, max_new_tokens)
+        lens = cache0.seq_len
+        nxt_logits = self._head(hid[torch.arange(B, device=dev), lens.long() - 1]).to(self.dtype).repeat_interleave(nb, 0)
+        del hid
+        # B prompts -> R = B * nb slots: slot r takes the prompt rows of prompt r // nb
+        k0 = cache0.kv
+        kv = KVCache(k0.k.shape[0], R, k0.k.shape[2], k0.cap, k0.k.shape[4], self.dtype, dev)
+        row0 = lens.repeat_interleave(nb).contiguous()                       # prompt length of every slot: generated rows start here
+        ops.kv_gather(k0.k, k0.v, kv.k, kv.v, (torch.arange(R, device=dev, dtype=torch.int32) // nb).contiguous(),
+                      torch.zeros(R, dtype=torch.int32, device=dev), row0, cache0.compact_len)
+        kv.length = k0.length
+        cache = AF3Cache(kv, row0.clone(), cache0.padded_len, cache0.compact_len)
+        del cache0, k0
+        kv_ws = torch.empty(max(lib.afhip_kv_gather_workspace_bytes(kv.k.shape[0], R, kv.k.shape[2], kv.k.shape[4], max_new_tokens,
+                                                                    L.dtype_code(self.dtype)), 1), dtype=torch.uint8, device=dev)
+
+        K = max(2, 1 + len(eos)) * nb
+        top_nb = torch.arange(K, device=dev) < nb
+        eos_t = torch.tensor(eos, dtype=torch.int64, device=dev)
+        fill = (pad if pad else eos[0]) if eos else -1                       # transformers: `pad or eos[0]`, -1 without an eos
+        running_seq = torch.full((B, nb, max_length), fill, dtype=torch.int64, device=dev)
+        running_seq[:, :, :W] = input_ids[:, None]
+        sequences = running_seq.clone()
+        running_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
+        running_scores[:, 1:] = -1e9
+        beam_scores = torch.full((B, nb), -1e9, dtype=torch.float32, device=dev)
+        finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
+        improvable = torch.ones((B, 1), dtype=torch.bool, device=dev)
+        running_bi = torch.full((B, nb, max_length - W), -1, dtype=torch.int32, device=dev)
+        beam_indices = running_bi.clone()
+        offs = torch.arange(B, device=dev)[:, None] * nb
+        scores, raw = [], []
+        cur_len = W
+        while True:
+            lg = nxt_logits.float().contiguous()
+            if out_logits:
+                raw.append(lg)
+            sc = torch.empty((R, V), dtype=torch.float32, device=dev) if out_scores else None
+            topv, topi = ops.beam_select(lg, running_scores, K, model_dtype=self.dtype, scores=sc)
+            if out_scores:
+                scores.append(sc)
+            # c. continuations
+            src_beam = topi // V
+            topk_seq = _gather_beams(running_seq, src_beam)
+            topk_seq[:, :, cur_len] = topi % V
+            topk_bi = _gather_beams(running_bi, src_beam)
+            topk_bi[:, :, cur_len - W] = (src_beam + offs).to(torch.int32)
+            # d. stopping criteria: an eos id, or max_length
+            hits = torch.isin(topk_seq[:, :, cur_len], eos_t) if eos else torch.zeros_like(top_nb[None].expand(B, K))
+            if cur_len + 1 >= max_length:
+                hits = torch.ones_like(hits)
+            # e. the best num_beams unfinished continuations run on
+            trl = topv + hits.to(torch.float32) * -1.0e9
+            nxt = torch.topk(trl, k=nb)[1]
+            running_seq, running_scores, running_bi = _gather_beams(topk_seq, nxt), _gather_beams(trl, nxt), _gather_beams(topk_bi, nxt)
+            # f. finished hypotheses
+            just = hits & top_nb[None, :]
+            fin = topv / ((cur_len + 1 - W) ** lp)
+            fin = fin + (finished.all(-1, keepdim=True) & (es is True)).to(torch.float32) * -1.0e9
+            fin = fin + (~improvable).to(torch.float32) * -1.0e9
+            fin = fin + (~just) * -1.0e9
+            keep = torch.topk(torch.cat((beam_scores, fin), 1), k=nb)[1]
+            sequences = _gather_beams(torch.cat((sequences, topk_seq), 1), keep)
+            beam_scores = _gather_beams(torch.cat((beam_scores, fin), 1), keep)
+            beam_indices = _gather_beams(torch.cat((beam_indices, topk_bi), 1), keep)
+            finished = _gather_beams(torch.cat((finished, just), 1), keep)
+            # g. early-stop heuristic and the loop condition
+            parent = running_bi[..., cur_len - W].reshape(R)
+            cur_len += 1
+            best_len = (max_length if es == "never" and lp > 0.0 else cur_len) - W
+            worst = torch.where(finished, beam_scores.min(1, keepdim=True)[0], -1.0e9)
+            improvable = improvable & (running_scores[:, :1] / (best_len ** lp) > worst).any(-1, keepdim=True)
+            go = improvable.any() & ~(finished.all() & (es is True)) & ~hits.all()
+            if not bool(go):
+                break
+            # the cache follows its beams: generated rows [prompt_len, seq_len) of every slot from its parent slot
+            if cur_len - 1 > W:
+                ops.kv_gather(kv.k, kv.v, kv.k, kv.v, parent.contiguous(), row0, cache.seq_len, cur_len - 1 - W, ws=kv_ws)
+            o = self.forward(input_ids=running_seq[:, :, cur_len - 1].reshape(R, 1), past_key_values=cache, use_cache=True)
+            nxt_logits = o.logits[:, -1]
+
+        sequences = sequences[:, :nrs].reshape(B * nrs, -1)
+        beam_scores = beam_scores[:, :nrs].reshape(B * nrs)
+        beam_indices = beam_indices[:, :nrs].reshape(B * nrs, -1)
+        n_gen = int((beam_indices + 1).bool().sum(1).max())
+        sequences, beam_indices = sequences[:, :W + n_gen], beam_indices[:, :n_gen]
+        if not cfg.get("return_dict_in_generate"):
+            return sequences
+        return SimpleNamespace(sequences=sequences, sequences_scores=beam_scores if out_scores else None,
+                               scores=tuple(scores) if out_scores else None, logits=tuple(raw) if out_logits else None,
+                               beam_indices=beam_indices, attentions=None, hidden_states=None, past_key_values=None)
 
     # ---- greedy generation (GenerationMixin.generate, do_sample=False)
     @torch.no_grad()

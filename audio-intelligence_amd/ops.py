@@ -363,3 +363,69 @@ def sample_filter(logits: torch.Tensor, *, temperature: float = 1.0, top_k: int 
     a.token = tok.data_ptr() if tok is not None else None
     L.check(lib.afhip_sample_filter(C.byref(a), C.c_void_p(ws.data_ptr()), need, L.stream_ptr()))
     return tok
+
+
+def beam_select(logits: torch.Tensor, running: torch.Tensor, K: int, *, model_dtype=torch.float32,
+                scores: Optional[torch.Tensor] = None):
+    """afhip_beam_select over f32 rows [B * nb, V] (any row stride; row b * nb + j = beam j of prompt b) and running beam scores
+    [B, nb] f32: per prompt the K largest fl32(log_softmax(row) + running) over its nb * V continuations, value descending, ties to
+    the smaller flat index j * V + id.  scores [B * nb, >= V] f32, when given, receives the log-prob rows.  Returns (values [B, K]
+    f32, flat indices [B, K] int64)."""
+    lib = L.lib()
+    _chk(logits, "beam_select.logits")
+    _chk(running, "beam_select.running")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise L.AfhipError("beam_select: logits must be f32 [B * nb, V] with unit column stride")
+    if running.dtype != torch.float32 or running.dim() != 2 or not running.is_contiguous():
+        raise L.AfhipError("beam_select: running must be contiguous f32 [B, nb]")
+    B, nb = running.shape
+    R, V = logits.shape
+    if R != B * nb:
+        raise L.AfhipError(f"beam_select: logits has {R} rows, running is [{B}, {nb}]")
+    if scores is not None:
+        _chk(scores, "beam_select.scores")
+        if scores.dtype != torch.float32 or scores.shape[0] != R or scores.shape[1] < V or scores.stride(1) != 1:
+            raise L.AfhipError(f"beam_select: scores must be f32 [{R}, >= {V}] with unit column stride")
+    need = lib.afhip_beam_select_workspace_bytes(B, nb, V, int(K))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=logits.device)
+    vals = torch.empty((B, int(K)), dtype=torch.float32, device=logits.device)
+    idx = torch.empty((B, int(K)), dtype=torch.int64, device=logits.device)
+    a = L.BeamSelectArgs()
+    a.logits, a.model_dtype, a.B, a.nb, a.V, a.ld = logits.data_ptr(), L.dtype_code(model_dtype), B, nb, V, logits.stride(0)
+    a.running, a.K, a.values, a.indices = running.data_ptr(), int(K), vals.data_ptr(), idx.data_ptr()
+    if scores is not None:
+        a.scores, a.ld_scores = scores.data_ptr(), scores.stride(0)
+    L.check(lib.afhip_beam_select(C.byref(a), C.c_void_p(ws.data_ptr()), need, L.stream_ptr()))
+    return vals, idx
+
+
+def kv_gather(src_k: torch.Tensor, src_v: torch.Tensor, dst_k: torch.Tensor, dst_v: torch.Tensor, parent: torch.Tensor,
+              row0: torch.Tensor, row1: torch.Tensor, max_rows: int, ws: Optional[torch.Tensor] = None):
+    """afhip_kv_gather: dst[l, r, h, t] = src[l, parent[r], h, t] (src as it was before the call) for t in [row0[r], row1[r]), on
+    caches [n_layers, B, n_kv, cap, hd] (bf16 or f32, contiguous; dst may be src: the in-place beam reorder).  parent / row0 / row1:
+    int32 [dst B] on the device; max_rows bounds row1 - row0.  `ws`: optional uint8 scratch of afhip_kv_gather_workspace_bytes,
+    reused across calls."""
+    lib = L.lib()
+    for name, t in (("src_k", src_k), ("src_v", src_v), ("dst_k", dst_k), ("dst_v", dst_v)):
+        _chk(t, f"kv_gather.{name}")
+        if t.dim() != 5 or not t.is_contiguous() or t.dtype != src_k.dtype:
+            raise L.AfhipError(f"kv_gather: {name} must be a contiguous [n_layers, B, n_kv, cap, hd] tensor of one dtype")
+    nl, Bs, nkv, cap, hd = src_k.shape
+    Bd = dst_k.shape[1]
+    if src_v.shape != src_k.shape or dst_v.shape != dst_k.shape or (dst_k.shape[0], dst_k.shape[2], dst_k.shape[3], dst_k.shape[4]) != (nl, nkv, cap, hd):
+        raise L.AfhipError("kv_gather: caches differ in n_layers / n_kv / cap / hd")
+    for name, t in (("parent", parent), ("row0", row0), ("row1", row1)):
+        _chk(t, f"kv_gather.{name}")
+        if t.dtype != torch.int32 or tuple(t.shape) != (Bd,) or not t.is_contiguous():
+            raise L.AfhipError(f"kv_gather: {name} must be contiguous int32 [{Bd}]")
+    dt = L.dtype_code(src_k.dtype)
+    in_place = src_k.data_ptr() == dst_k.data_ptr()
+    need = lib.afhip_kv_gather_workspace_bytes(nl, Bd, nkv, hd, int(max_rows), dt) if in_place else 0
+    if need and (ws is None or ws.numel() < need):
+        ws = torch.empty(need, dtype=torch.uint8, device=src_k.device)
+    src, dst = L.KvCache(), L.KvCache()
+    src.k, src.v, src.cap, src.B = src_k.data_ptr(), src_v.data_ptr(), cap, Bs
+    dst.k, dst.v, dst.cap, dst.B = dst_k.data_ptr(), dst_v.data_ptr(), cap, Bd
+    L.check(lib.afhip_kv_gather(C.byref(src), C.byref(dst), nl, nkv, hd, dt, parent.data_ptr(), row0.data_ptr(), row1.data_ptr(),
+                                int(max_rows), L.ptr(ws if need else None), need, L.stream_ptr()))
+    return ws

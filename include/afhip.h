@@ -482,6 +482,40 @@ typedef struct {
 size_t afhip_sample_filter_workspace_bytes(int rows, int V);
 int afhip_sample_filter(const afhip_sample_filter_args* args, void* ws, size_t ws_bytes, void* stream);
 
+/* Beam-search candidate selection (beam.hip): step b-c of transformers' GenerationMixin._beam_search for B prompts of nb beams.
+ * Row r = b * nb + j of `logits` holds beam j of prompt b.  For every id v of every row:
+ *   logp[r, v] = fl32(fl32(x - m_r) - logf(s_r))          (torch's log_softmax; m_r row maximum, s_r = sum exp(x - m_r))
+ *   cand[r, v] = fl32(logp[r, v] + running[r])
+ * and per prompt the K largest cand over its nb * V ids, in order of value descending, ties to the smaller flat index j * V + v.
+ * The selection is exact on cand itself (not on the logits).  Rows are split into 8192-id chunks: chunk statistics, then every
+ * chunk's own top K of cand, then one merge per prompt.  Bit-identical across launches and whether or not `scores` is requested.
+ * No allocation, no host synchronisation.  Scratch is the caller's `ws` of afhip_beam_select_workspace_bytes. */
+typedef struct {
+    const float* logits;       /* [B * nb, ld] f32 */
+    int model_dtype;           /* AFHIP_BF16: every logit is rounded to bf16 first (the head output in the model dtype, cast to f32) */
+    int B, nb, V, ld;          /* nb 1..32, V <= ld, V < 2^23 */
+    const float* running;      /* [B, nb] f32 running beam scores */
+    int K;                     /* 1..128 and <= nb * V (HF: max(2, 1 + n_eos) * nb) */
+    float* values;             /* [B, K] out: cand of the selected candidates */
+    int64_t* indices;          /* [B, K] out: their flat index j * V + v */
+    float* scores;             /* [B * nb, ld_scores] out or NULL: logp (HF's `scores` entry of the step) */
+    int ld_scores;
+} afhip_beam_select_args;
+size_t afhip_beam_select_workspace_bytes(int B, int nb, int V, int K);
+int afhip_beam_select(const afhip_beam_select_args* args, void* ws, size_t ws_bytes, void* stream);
+
+/* KV-cache slot gather (beam.hip) between two caches of the same cap / n_kv / hd / dtype ([n_layers, B, n_kv, cap, hd] each):
+ * for every layer, kv head and slot r < dst->B, rows t in [row0[r], row1[r]) of slot r of dst become rows t of slot parent[r] of
+ * src AS IT WAS before the call.  parent / row0 / row1: device int32 [dst->B]; max_rows (host) >= every row1[r] - row0[r] sizes the
+ * grid (longer ranges are cut to max_rows; ranges are clipped to [0, cap); a parent outside [0, src->B) leaves the slot as is).
+ * Rows outside the range are never touched.  src == dst (same k / v) is the in-place reorder of beam search: a slot whose parent is
+ * itself costs nothing, and a slot is staged through the workspace only when its parent is itself overwritten -- swaps, cycles and
+ * many-from-one maps come out right and at most 2 x (slots with parent[r] != r) x range bytes move.  Two launches, no allocation,
+ * no host synchronisation.  ws >= afhip_kv_gather_workspace_bytes (in place; out of place needs none). */
+size_t afhip_kv_gather_workspace_bytes(int n_layers, int B, int n_kv, int hd, int max_rows, int dtype);
+int afhip_kv_gather(const afhip_kv_cache* src, const afhip_kv_cache* dst, int n_layers, int n_kv, int hd, int dtype, const int32_t* parent,
+                    const int32_t* row0, const int32_t* row1, int max_rows, void* ws, size_t ws_bytes, void* stream);
+
 /* One greedy decode step for B sequences entirely on device: embed prev token (stream 0 = token, others pad),
  * forward 1 position, lm_head on stream 0, masked argmax, append to out_tokens[step], update finished flags
  * (eos/eot, lm/parallel.py:503-513).  No host sync. */
